@@ -13,6 +13,19 @@ overlapped bucketed all-reduce, fused SGD update), bracketed by
 barrier + torch.cuda.synchronize on both sides; MAX elapsed over ranks.
 Synthetic ImageNet-shape data (3x224x224), random-init weights, bf16
 compute with fp32 optimizer state.
+
+A plain run sets up, warms up, times the K steps and prints the result
+line. --dump-outputs DIR additionally saves the last timed step's loss,
+logits and a seeded sample of the updated parameters as float32 .npy
+files. Weights and input batches are seeded, but the weight-grad and loss
+kernels accumulate with atomics, and K steps of lr=0.1 training amplify
+that last-bit noise into visibly different weights. So with
+--dump-outputs the last timed step starts again from the seeded initial
+state (weights, BN statistics, zero momentum; a device-to-device copy of
+well under 1% of a step): its inputs, and hence what it computes, are
+the same in every run and comparable between two builds.
+--full is reserved for secondary measurements that need runs of their
+own; a plain run never pays for them.
 """
 
 from __future__ import annotations
@@ -66,7 +79,71 @@ def parse_args():
                    help="channels_last (NHWC) keeps MIOpen on its native "
                         "xdlops conv solvers and our BN kernels on the "
                         "coalesced NHWC path")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed "
+                        "step computed (loss, logits, a seeded sample of "
+                        "the updated parameters) as DIR/<name>.npy, float32; "
+                        "that step restarts from the seeded initial state "
+                        "so that every run computes the same")
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements that a plain "
+                        "run skips (none yet: every figure in the result "
+                        "line comes from the timed steps themselves)")
     return p.parse_args()
+
+
+# per-array element cap for --dump-outputs: ~160 parameter tensors of
+# <= 16384 sampled values plus the logits stay far below 64 MB
+_DUMP_CAP = 16384
+_DUMP_CAP_LOGITS = 1 << 22
+
+
+def _dump_sample(t, cap, gen):
+    """Flattened float32 CPU copy of ``t``; tensors above ``cap`` elements
+    are reduced to ``cap`` positions drawn from the seeded ``gen`` (same
+    positions every run)."""
+    flat = t.detach().reshape(-1)
+    if flat.numel() > cap:
+        idx = torch.randint(flat.numel(), (cap,), generator=gen)
+        flat = flat[idx.to(flat.device)]
+    return flat.float().cpu()
+
+
+class _InitialState:
+    """Copy of the model's parameters and buffers, taken before the first
+    step, to restart the dumped step from the same state in every run."""
+
+    def __init__(self, model, opt):
+        self.live = [t.detach() for t in model.parameters()]
+        self.live += list(model.buffers())
+        self.saved = [t.clone() for t in self.live]
+        self.opt = opt
+
+    @torch.no_grad()
+    def restore(self):
+        torch._foreach_copy_(self.live, self.saved)
+        # zero momentum == no momentum yet: the next update sets it to
+        # the step's own gradient, as the very first update does
+        moms = [st["momentum_buffer"] for st in self.opt.state.values()
+                if "momentum_buffer" in st]
+        if moms:
+            torch._foreach_zero_(moms)
+
+
+def dump_outputs(dirname, loss, logits, model):
+    """Write the last timed step's results for build-vs-build comparison."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    gen = torch.Generator().manual_seed(2024)
+    np.save(os.path.join(dirname, "loss.npy"),
+            loss.detach().float().cpu().numpy())
+    lg = _dump_sample(logits, _DUMP_CAP_LOGITS, gen)
+    if lg.numel() == logits.numel():
+        lg = lg.view(logits.shape)
+    np.save(os.path.join(dirname, "logits.npy"), lg.numpy())
+    params = torch.cat([_dump_sample(p, _DUMP_CAP, gen)
+                        for p in model.parameters()])
+    np.save(os.path.join(dirname, "params.npy"), params.numpy())
 
 
 def main():
@@ -122,6 +199,7 @@ def main():
     dp = BucketedDataParallel(model)
     opt = FusedSGD(model.parameters(), lr=0.1 * world, momentum=0.9,
                    weight_decay=1e-4, backend=cfg.kernel_backend)
+    initial = _InitialState(model, opt) if args.dump_outputs else None
 
     # synthetic device-resident batches, rotated so no step reuses the
     # previous step's input (no caching of outputs; all compute runs)
@@ -144,7 +222,7 @@ def main():
         loss.backward()
         dp.finalize_backward()
         opt.step()
-        return loss
+        return loss, out
 
     # hipGraph-captured step (single GPU): replays the whole
     # fwd+loss+bwd+fused-SGD step as one graph — removes every
@@ -158,7 +236,7 @@ def main():
         model.zero_grad(set_to_none=False)
         loss.backward()
         opt.step()
-        return loss
+        return loss, out
 
     use_graph = (args.hipgraph != "off" and device.type == "cuda"
                  and world == 1 and args.strategy == "ddp")
@@ -170,15 +248,17 @@ def main():
         try:
             gpool = torch.cuda.graphs.graph_pool_handle()
             graphs = []
+            gouts = []  # static (loss, logits) tensors of each graph
             for i in range(n_pool):
                 gr = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(gr, pool=gpool):
-                    gstep(i)
+                    gouts.append(gstep(i))
                 graphs.append(gr)
             torch.cuda.synchronize(device)
 
-            def step_fn(i, _g=graphs):
+            def step_fn(i, _g=graphs, _o=gouts):
                 _g[i % n_pool].replay()
+                return _o[i % n_pool]
             if env.rank == 0:
                 print("# hipGraph-captured step (4 graphs)",
                       file=sys.stderr)
@@ -206,8 +286,11 @@ def main():
     t0 = time.perf_counter()
     if events:
         events[0].record()
+    last = None
     for i in range(args.steps):
-        step_fn(args.warmup + i)
+        if initial is not None and i == args.steps - 1:
+            initial.restore()
+        last = step_fn(args.warmup + i)
         if events:
             events[i + 1].record()
     barrier_sync()
@@ -223,6 +306,9 @@ def main():
                          device=device if device.type == "cuda" else "cpu")
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = t.item()
+
+    if env.rank == 0 and args.dump_outputs and last is not None:
+        dump_outputs(args.dump_outputs, last[0], last[1], model)
 
     if env.rank == 0:
         total_images = args.steps * args.batch * world

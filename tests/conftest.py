@@ -1,13 +1,20 @@
+import atexit
 import os
+import shutil
 import tempfile
 
 import pytest
 import torch
 
-# keep test-generated profiler artifacts out of the committed profiles/
-os.environ.setdefault("DDLB_PROFILE_DIR",
-                      os.path.join(tempfile.gettempdir(),
-                                   "ddlb_test_profiles"))
+# keep test-generated profiler artifacts out of the committed profiles/:
+# a directory private to this run (a fixed shared name under the temp dir
+# breaks as soon as another user has created it); child processes inherit
+# the variable and reuse it
+if "DDLB_PROFILE_DIR" not in os.environ:
+    os.environ["DDLB_PROFILE_DIR"] = tempfile.mkdtemp(
+        prefix="ddlb_test_profiles_")
+    atexit.register(shutil.rmtree, os.environ["DDLB_PROFILE_DIR"],
+                    ignore_errors=True)
 
 
 def pytest_configure(config):

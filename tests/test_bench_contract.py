@@ -40,6 +40,53 @@ def test_dataset_flag():
     assert d["config"]["input"] == "3x32x32"
 
 
+def test_dump_outputs_and_full(tmp_path):
+    """--dump-outputs writes the last timed step's results as float32
+    .npy files (well under the 64 MB budget) and a rerun with the same
+    arguments sees the same inputs; --full is accepted and keeps the
+    result line."""
+    import numpy as np
+    small = ("--dataset", "mnist", "--model", "resnet18")
+    runs = []
+    for name, extra in (("a", ()), ("b", ("--full",))):
+        d = _run(*small, *extra, "--dump-outputs", str(tmp_path / name))
+        assert REQUIRED.issubset(d) and d["steps"] == 2
+        files = sorted(p.name for p in (tmp_path / name).iterdir())
+        assert files == ["logits.npy", "loss.npy", "params.npy"]
+        arrs = {f: np.load(tmp_path / name / f) for f in files}
+        assert all(a.dtype == np.float32 for a in arrs.values())
+        assert all(np.isfinite(a).all() for a in arrs.values())
+        assert arrs["logits.npy"].shape == (4, 10)
+        assert arrs["loss.npy"].shape == ()
+        assert sum(a.nbytes for a in arrs.values()) < 64 * 2**20
+        runs.append(arrs)
+    # same seeds, same arguments: fp32 CPU results agree up to the
+    # reduction order of the threaded library kernels
+    for f in runs[0]:
+        np.testing.assert_allclose(runs[0][f], runs[1][f],
+                                   rtol=1e-4, atol=1e-5)
+
+
+def test_dump_outputs_do_not_depend_on_earlier_steps(tmp_path):
+    """The dumped step restarts from the seeded initial state, so what it
+    computes depends only on its own batch: 2 warmup + 3 timed steps end
+    on the same batch (index 4 % 4 == 0) as a single first step and must
+    dump the same loss, logits and updated parameters. Without the restart
+    four lr=0.1 updates would have moved the weights far beyond the
+    tolerance."""
+    import numpy as np
+    small = ("--dataset", "mnist", "--model", "resnet18")
+    _run(*small, "--steps", "1", "--warmup", "0",
+         "--dump-outputs", str(tmp_path / "one"))
+    d = _run(*small, "--steps", "3", "--warmup", "2",
+             "--dump-outputs", str(tmp_path / "five"))
+    assert d["steps"] == 3 and d["warmup"] == 2
+    for f in ("loss.npy", "logits.npy", "params.npy"):
+        np.testing.assert_allclose(np.load(tmp_path / "one" / f),
+                                   np.load(tmp_path / "five" / f),
+                                   rtol=1e-4, atol=1e-5)
+
+
 def test_torchrun_8rank_driver_command(tmp_path):
     """The exact driver launch shape: torch.distributed.run --nnodes=1
     --nproc-per-node 8 ... bench.py --gpus 8 (CPU/gloo plumbing) must
