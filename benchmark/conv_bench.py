@@ -4,7 +4,10 @@
 Times forward and data-grad over the ResNet-50 layer shapes (bf16,
 channels_last) and prints one JSON line per shape with ms and effective
 TFLOP/s for both backends — the measurement that drives the conv
-dispatch policy."""
+dispatch policy.
+
+``--stem`` instead times the small-C stem convs the model zoo builds
+(native csrc/conv_stem.hip vs the library), forward and weight-grad."""
 
 import argparse
 import json
@@ -39,14 +42,98 @@ def bench_op(fn, iters, warmup):
     return (time.perf_counter() - t0) / iters
 
 
+# HBM peak used for the byte-bound floor of the stem rows (MI355X, TB/s)
+HBM_TBS = 8.0
+
+
+def stem_shapes(batch):
+    """(dataset, arch, batch, conv, H, W) for every distinct stem the model
+    zoo builds, read off the models themselves."""
+    import torch.nn as nn
+    from ddlbench_amd.config import DATASET_SHAPES
+    from ddlbench_amd.models import build_model
+    from ddlbench_amd.ops.conv import stem_eligible
+    seen, out = set(), []
+    for dataset, n in (("imagenet", batch), ("highres", 32),
+                       ("cifar10", batch), ("mnist", batch)):
+        _, H, W = DATASET_SHAPES[dataset][:3]
+        for arch in ("resnet50", "vgg16", "mobilenetv2"):
+            model = build_model(dataset, arch)
+            conv = next(m for m in model.modules()
+                        if isinstance(m, nn.Conv2d))
+            if not stem_eligible(conv):
+                continue
+            key = (dataset, conv.in_channels, conv.out_channels,
+                   conv.kernel_size, conv.stride, conv.padding)
+            if key not in seen:
+                seen.add(key)
+                out.append((dataset, arch, n, conv, H, W))
+    return out
+
+
+def bench_stem(args):
+    from ddlbench_amd.ops import require_extension
+    ext = require_extension()
+    dev = torch.device("cuda", 0)
+    cl = torch.channels_last
+    for dataset, arch, N, conv, H, W in stem_shapes(args.batch):
+        C, K, R = conv.in_channels, conv.out_channels, conv.kernel_size[0]
+        stride, pad = conv.stride[0], conv.padding[0]
+        x = torch.randn(N, C, H, W, device=dev,
+                        dtype=torch.bfloat16).contiguous(memory_format=cl)
+        w = torch.randn(K, C, R, R, device=dev,
+                        dtype=torch.bfloat16).contiguous(memory_format=cl)
+        OH = (H + 2 * pad - R) // stride + 1
+        OW = (W + 2 * pad - R) // stride + 1
+        dy = torch.randn(N, K, OH, OW, device=dev,
+                         dtype=torch.bfloat16).contiguous(memory_format=cl)
+        fns = {
+            "native_fwd": lambda: ext.conv_stem_fwd(x, w, stride, pad),
+            "library_fwd": lambda: torch.nn.functional.conv2d(
+                x, w, None, stride, pad),
+            "native_wgrad": lambda: ext.conv_stem_wgrad(
+                x, dy, R, R, stride, pad),
+            "library_wgrad": lambda: torch.ops.aten.convolution_backward(
+                dy, x, w, None, [stride, stride], [pad, pad], [1, 1],
+                False, [0, 0], 1, [False, True, False]),
+        }
+        res = {"dataset": dataset, "arch": arch,
+               "shape": f"C{C}_H{H}_W{W}_K{K}_R{R}_s{stride}_p{pad}",
+               "batch": N}
+        # native and library alternate; two passes, the lower time counts
+        best = {}
+        for _ in range(2):
+            for name, fn in fns.items():
+                t = bench_op(fn, args.iters, args.warmup)
+                best[name] = min(best.get(name, t), t)
+        for name, t in best.items():
+            res[name + "_ms"] = round(t * 1e3, 4)
+        # byte-bound floors: fwd x + w + y, wgrad x + dy
+        fwd_b = 2 * (x.numel() + w.numel() + dy.numel())
+        wg_b = 2 * (x.numel() + dy.numel())
+        res["fwd_floor_ms"] = round(fwd_b / (HBM_TBS * 1e12) * 1e3, 4)
+        res["wgrad_floor_ms"] = round(wg_b / (HBM_TBS * 1e12) * 1e3, 4)
+        res["fwd_floor_share"] = round(
+            fwd_b / (HBM_TBS * 1e12) / best["native_fwd"], 3)
+        res["wgrad_floor_share"] = round(
+            wg_b / (HBM_TBS * 1e12) / best["native_wgrad"], 3)
+        print(json.dumps(res), flush=True)
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--batch", type=int, default=256)
     p.add_argument("--iters", type=int, default=10)
     p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--stem", action="store_true",
+                   help="time the model zoo's stem convs (native vs "
+                        "library, forward and weight-grad) instead")
     args = p.parse_args()
     assert torch.cuda.is_available()
     torch.backends.cudnn.benchmark = True
+    if args.stem:
+        bench_stem(args)
+        return
     from ddlbench_amd.ops.conv import conv2d_mfma
     dev = torch.device("cuda", 0)
     cl = torch.channels_last

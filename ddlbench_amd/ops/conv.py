@@ -5,8 +5,12 @@ Forward and data-grad run on the hand-written NHWC bf16 kernels
 (csrc/conv_wgrad.hip) — the full conv triple is in-tree by default.
 
 Eligibility: bf16, channels_last, groups=1, dilation=1, C%8==0, K%8==0.
-``convert_convs(model)`` swaps every eligible nn.Conv2d for Conv2dMFMA
-(stem convs with C=3 stay on the library path)."""
+``convert_convs(model)`` swaps every eligible nn.Conv2d for Conv2dMFMA.
+
+Stem convs (C < 8) stay on the library path by default; with
+``DDLB_STEM=native`` (or ``convert_convs(model, stem="native")``) they run
+the small-C kernels of csrc/conv_stem.hip (forward + weight-grad) through
+``Conv2dStem``."""
 
 from __future__ import annotations
 
@@ -105,15 +109,117 @@ class Conv2dMFMA(nn.Module):
                 f"pad={self.padding} [mfma]")
 
 
-def convert_convs(model: nn.Module, dtype=torch.bfloat16) -> int:
+class _ConvStem(torch.autograd.Function):
+    """Small-C stem conv: native forward and weight-grad (cast back to the
+    weight dtype). There is no native data-grad — stem inputs are data; if
+    the input does require a gradient, dx comes from the library
+    (aten.convolution_backward)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, stride, pad):
+        ext = _ops.require_extension()
+        x = x.contiguous(memory_format=_CL)
+        w = weight.contiguous(memory_format=_CL)
+        y = ext.conv_stem_fwd(x, w, stride, pad)
+        ctx.save_for_backward(x, weight)
+        ctx.stride = stride
+        ctx.pad = pad
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        ext = _ops.require_extension()
+        x, weight = ctx.saved_tensors
+        dy = dy.contiguous(memory_format=_CL)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.ops.aten.convolution_backward(
+                dy, x, weight, None, [ctx.stride, ctx.stride],
+                [ctx.pad, ctx.pad], [1, 1], False, [0, 0], 1,
+                [True, False, False])[0]
+        if ctx.needs_input_grad[1]:
+            R = weight.shape[2]
+            dw32 = ext.conv_stem_wgrad(x, dy, R, weight.shape[3],
+                                       ctx.stride, ctx.pad)
+            # (K, R*S*C) memory -> logical (K,C,R,S) channels_last
+            dw = dw32.view(weight.shape[0], R, weight.shape[3],
+                           weight.shape[1]) \
+                .permute(0, 3, 1, 2).to(weight.dtype)
+        return dx, dw, None, None
+
+
+def conv2d_stem(x, weight, stride=1, pad=0):
+    return _ConvStem.apply(x, weight, stride, pad)
+
+
+def stem_eligible(conv: nn.Conv2d, x_dtype=torch.bfloat16) -> bool:
+    """True for the shapes csrc/conv_stem.hip supports: C in 1..4, square
+    3/5/7 kernel, stride 1 or 2, 0 <= pad <= R/2, K % 8 == 0, K <= 128,
+    no bias, groups=1, dilation=1."""
+    return (x_dtype == torch.bfloat16
+            and conv.groups == 1
+            and conv.dilation == (1, 1)
+            and conv.bias is None
+            and 1 <= conv.in_channels <= 4
+            and conv.out_channels % 8 == 0
+            and 8 <= conv.out_channels <= 128
+            and conv.kernel_size[0] == conv.kernel_size[1]
+            and conv.kernel_size[0] in (3, 5, 7)
+            and conv.stride[0] == conv.stride[1]
+            and conv.stride[0] in (1, 2)
+            and not isinstance(conv.padding, str)
+            and conv.padding[0] == conv.padding[1]
+            and 0 <= conv.padding[0] <= conv.kernel_size[0] // 2)
+
+
+class Conv2dStem(nn.Module):
+    """Drop-in for a stem_eligible nn.Conv2d, running the stem kernels.
+    Shares the conv's weight Parameter, so state_dict keys are unchanged."""
+
+    def __init__(self, conv: nn.Conv2d):
+        super().__init__()
+        self.in_channels = conv.in_channels
+        self.out_channels = conv.out_channels
+        self.kernel_size = conv.kernel_size
+        self.stride = conv.stride[0]
+        self.padding = conv.padding[0]
+        self.weight = conv.weight
+
+    def forward(self, x):
+        if x.is_cuda and x.dtype == torch.bfloat16:
+            return conv2d_stem(x, self.weight, self.stride, self.padding)
+        return F.conv2d(x, self.weight, None, self.stride, self.padding)
+
+    def extra_repr(self):
+        return (f"{self.in_channels}, {self.out_channels}, "
+                f"k={self.kernel_size}, stride={self.stride}, "
+                f"pad={self.padding} [stem]")
+
+
+def convert_convs(model: nn.Module, dtype=torch.bfloat16,
+                  stem=None) -> int:
     """Replace eligible nn.Conv2d children with Conv2dMFMA and eligible
     nn.MaxPool2d with the native NHWC pool. Returns the number of
-    conversions."""
+    conversions.
+
+    ``stem`` selects the path of small-C stem convs: "library" (default)
+    leaves them as nn.Conv2d, "native" swaps stem_eligible ones for
+    Conv2dStem and counts them. ``stem=None`` reads DDLB_STEM at call
+    time."""
+    if stem is None:
+        stem = os.environ.get("DDLB_STEM", "library")
+    if stem not in ("native", "library"):
+        raise ValueError(f"stem must be 'native' or 'library', got {stem!r}")
     count = 0
     for parent in model.modules():
         for name, child in list(parent.named_children()):
-            if isinstance(child, nn.Conv2d) and mfma_eligible(child, dtype):
+            if not isinstance(child, nn.Conv2d):
+                continue
+            if mfma_eligible(child, dtype):
                 setattr(parent, name, Conv2dMFMA(child))
+                count += 1
+            elif stem == "native" and stem_eligible(child, dtype):
+                setattr(parent, name, Conv2dStem(child))
                 count += 1
     if dtype == torch.bfloat16 and \
             os.environ.get("DDLB_MAXPOOL", "1") != "0":

@@ -63,6 +63,13 @@ void launch_conv_wgrad(const void*, const void*, float*, float*, long,
                        int, int, int, int, int, int, int, int, int, int,
                        hipStream_t);
 
+void launch_conv_stem_fwd(const void*, const void*, void*, int, int, int,
+                          int, int, int, int, int, int, int, hipStream_t);
+void launch_conv_stem_wgrad(const void*, const void*, float*, float*, int,
+                            int, int, int, int, int, int, int, int, int,
+                            hipStream_t);
+int conv_stem_wgrad_chunks(int N, int OH, int OW, int K);
+
 void launch_maxpool_fwd(const void*, void*, unsigned char*, int64_t,
                         int64_t, int, int, int, int, int, int, int,
                         hipStream_t);
@@ -447,6 +454,85 @@ torch::Tensor conv_igemm_wgrad(torch::Tensor x, torch::Tensor dy,
   return dw;
 }
 
+// ---- stem conv (C < 8, NHWC bf16) -------------------------------------
+// Shape limits of csrc/conv_stem.hip; a violation raises before any
+// launch.
+static void check_stem_shape(int64_t C, int64_t K, int64_t R, int64_t S,
+                             int64_t stride, int64_t pad) {
+  TORCH_CHECK(C >= 1 && C <= 4, "conv_stem needs 1 <= C <= 4");
+  TORCH_CHECK(R == S && (R == 3 || R == 5 || R == 7),
+              "conv_stem needs a square 3x3, 5x5 or 7x7 kernel");
+  TORCH_CHECK(stride == 1 || stride == 2, "conv_stem needs stride 1 or 2");
+  TORCH_CHECK(pad >= 0 && pad <= R / 2, "conv_stem needs 0 <= pad <= R/2");
+  TORCH_CHECK(K % 8 == 0 && K >= 8 && K <= 128,
+              "conv_stem needs K % 8 == 0 and K <= 128");
+}
+
+// x: (N,C,H,W) channels_last; w: (K,C,R,R) channels_last (= (K, R*R*C)
+// row-major memory). Returns channels_last y.
+torch::Tensor conv_stem_fwd(torch::Tensor x, torch::Tensor w,
+                            int64_t stride, int64_t pad) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 &&
+                  w.is_cuda() && w.scalar_type() == at::kBFloat16,
+              "conv_stem: bf16 HIP tensors only");
+  TORCH_CHECK(x.dim() == 4 && w.dim() == 4, "conv_stem: 4-D tensors only");
+  TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast),
+              "x must be channels_last");
+  TORCH_CHECK(w.is_contiguous(at::MemoryFormat::ChannelsLast),
+              "w must be channels_last");
+  const int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  const int K = w.size(0), R = w.size(2), S = w.size(3);
+  TORCH_CHECK(w.size(1) == C, "conv_stem: weight C mismatch");
+  check_stem_shape(C, K, R, S, stride, pad);
+  const int OH = (H + 2 * (int)pad - R) / (int)stride + 1;
+  const int OW = (W + 2 * (int)pad - S) / (int)stride + 1;
+  TORCH_CHECK(N >= 1 && H + 2 * pad >= R && W + 2 * pad >= S,
+              "conv_stem: empty output");
+  auto y = torch::empty({N, K, OH, OW},
+                        x.options().memory_format(
+                            at::MemoryFormat::ChannelsLast));
+  launch_conv_stem_fwd(x.data_ptr(), w.data_ptr(), y.data_ptr(), N, H, W, C,
+                       K, OH, OW, R, (int)stride, (int)pad, cur_stream());
+  return y;
+}
+
+// x: (N,C,H,W) channels_last; dy: (N,K,OH,OW) channels_last. Returns fp32
+// dw in (K, R*S*C) memory — the conv_igemm_wgrad convention.
+torch::Tensor conv_stem_wgrad(torch::Tensor x, torch::Tensor dy, int64_t R,
+                              int64_t S, int64_t stride, int64_t pad) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 &&
+                  dy.is_cuda() && dy.scalar_type() == at::kBFloat16,
+              "conv_stem: bf16 HIP tensors only");
+  TORCH_CHECK(x.dim() == 4 && dy.dim() == 4, "conv_stem: 4-D tensors only");
+  TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast),
+              "x must be channels_last");
+  TORCH_CHECK(dy.is_contiguous(at::MemoryFormat::ChannelsLast),
+              "dy must be channels_last");
+  const int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  const int K = dy.size(1), OH = dy.size(2), OW = dy.size(3);
+  check_stem_shape(C, K, R, S, stride, pad);
+  TORCH_CHECK(N >= 1 && dy.size(0) == N && OH >= 1 && OW >= 1 &&
+                  OH == (H + 2 * pad - R) / stride + 1 &&
+                  OW == (W + 2 * pad - S) / stride + 1,
+              "conv_stem: dy shape does not match x");
+  const int64_t total = (int64_t)K * R * S * C;
+  auto dw = torch::empty({K, R * S * C}, x.options().dtype(at::kFloat));
+  // per-block partial slabs (cached per device, grown on demand); every
+  // slab element the combine reads is written by the same call
+  static std::unordered_map<int, torch::Tensor> stws;
+  const int devi = (int)x.get_device();
+  const int64_t need = total * conv_stem_wgrad_chunks(N, OH, OW, K);
+  auto wit = stws.find(devi);
+  if (wit == stws.end() || wit->second.numel() < need) {
+    stws[devi] = torch::empty({need}, x.options().dtype(at::kFloat));
+    wit = stws.find(devi);
+  }
+  launch_conv_stem_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr<float>(),
+                         wit->second.data_ptr<float>(), N, H, W, C, K, OH,
+                         OW, (int)R, (int)stride, (int)pad, cur_stream());
+  return dw;
+}
+
 // ---- NHWC max-pool ----------------------------------------------------
 std::vector<torch::Tensor> maxpool_fwd(torch::Tensor x, int64_t k,
                                        int64_t stride, int64_t pad) {
@@ -588,6 +674,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "NHWC bf16 MFMA implicit-GEMM conv data-grad");
   m.def("conv_igemm_wgrad", &conv_igemm_wgrad,
         "NHWC bf16 MFMA implicit-GEMM conv weight-grad (fp32 out)");
+  m.def("conv_stem_fwd", &conv_stem_fwd,
+        "NHWC bf16 MFMA stem conv (C < 8) forward");
+  m.def("conv_stem_wgrad", &conv_stem_wgrad,
+        "NHWC bf16 MFMA stem conv (C < 8) weight-grad (fp32 out)");
   m.def("ce_fwd", &ce_fwd, "cross-entropy forward");
   m.def("ce_bwd", &ce_bwd, "cross-entropy backward");
   m.def("revert_varlen", &revert_varlen,

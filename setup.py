@@ -27,6 +27,7 @@ KERNEL_SOURCES = [
     "bn_act.hip",
     "conv_mfma.hip",
     "conv_mfma2.hip",
+    "conv_stem.hip",
     "conv_wgrad.hip",
     "cross_entropy.hip",
     "depthwise_conv.hip",
