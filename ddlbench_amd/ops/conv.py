@@ -29,6 +29,13 @@ _WGRAD = os.environ.get("DDLB_WGRAD", "mfma")
 _CL = torch.channels_last
 
 
+def _dw_to_weight_layout(dw32, weight):
+    """fp32 (K, R*S*C) memory -> logical (K,C,R,S) channels_last in the
+    weight's dtype."""
+    K, C, R, S = weight.shape
+    return dw32.view(K, R, S, C).permute(0, 3, 1, 2).to(weight.dtype)
+
+
 class _ConvMFMA(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, stride, pad):
@@ -55,13 +62,10 @@ class _ConvMFMA(torch.autograd.Function):
                                       ctx.pad)
         if ctx.needs_input_grad[1]:
             if _WGRAD == "mfma":
-                R = weight.shape[2]
-                dw32 = ext.conv_igemm_wgrad(x, dy, R, weight.shape[3],
-                                            ctx.stride, ctx.pad)
-                # (K, R*S*C) memory -> logical (K,C,R,S) channels_last
-                dw = dw32.view(weight.shape[0], R, weight.shape[3],
-                               weight.shape[1]) \
-                    .permute(0, 3, 1, 2).to(weight.dtype)
+                dw = _dw_to_weight_layout(
+                    ext.conv_igemm_wgrad(x, dy, weight.shape[2],
+                                         weight.shape[3], ctx.stride,
+                                         ctx.pad), weight)
             else:
                 dw = torch.ops.aten.convolution_backward(
                     dy, x, weight, None, [ctx.stride, ctx.stride],
@@ -86,8 +90,12 @@ def mfma_eligible(conv: nn.Conv2d, x_dtype=torch.bfloat16) -> bool:
             and conv.kernel_size[0] == conv.kernel_size[1])
 
 
-class Conv2dMFMA(nn.Module):
-    """Drop-in for an eligible nn.Conv2d, running the MFMA kernel."""
+class _NativeConv2d(nn.Module):
+    """Drop-in for a square, bias-free nn.Conv2d. Shares the conv's weight
+    Parameter, so state_dict keys are unchanged; bf16 device inputs run
+    the subclass's native kernel, anything else F.conv2d."""
+
+    tag = ""
 
     def __init__(self, conv: nn.Conv2d):
         super().__init__()
@@ -98,15 +106,27 @@ class Conv2dMFMA(nn.Module):
         self.padding = conv.padding[0]
         self.weight = conv.weight
 
+    def native(self, x):
+        raise NotImplementedError
+
     def forward(self, x):
         if x.is_cuda and x.dtype == torch.bfloat16:
-            return conv2d_mfma(x, self.weight, self.stride, self.padding)
+            return self.native(x)
         return F.conv2d(x, self.weight, None, self.stride, self.padding)
 
     def extra_repr(self):
         return (f"{self.in_channels}, {self.out_channels}, "
                 f"k={self.kernel_size}, stride={self.stride}, "
-                f"pad={self.padding} [mfma]")
+                f"pad={self.padding} [{self.tag}]")
+
+
+class Conv2dMFMA(_NativeConv2d):
+    """Drop-in for an eligible nn.Conv2d, running the MFMA kernel."""
+
+    tag = "mfma"
+
+    def native(self, x):
+        return conv2d_mfma(x, self.weight, self.stride, self.padding)
 
 
 class _ConvStem(torch.autograd.Function):
@@ -138,13 +158,9 @@ class _ConvStem(torch.autograd.Function):
                 [ctx.pad, ctx.pad], [1, 1], False, [0, 0], 1,
                 [True, False, False])[0]
         if ctx.needs_input_grad[1]:
-            R = weight.shape[2]
-            dw32 = ext.conv_stem_wgrad(x, dy, R, weight.shape[3],
-                                       ctx.stride, ctx.pad)
-            # (K, R*S*C) memory -> logical (K,C,R,S) channels_last
-            dw = dw32.view(weight.shape[0], R, weight.shape[3],
-                           weight.shape[1]) \
-                .permute(0, 3, 1, 2).to(weight.dtype)
+            dw = _dw_to_weight_layout(
+                ext.conv_stem_wgrad(x, dy, weight.shape[2], weight.shape[3],
+                                    ctx.stride, ctx.pad), weight)
         return dx, dw, None, None
 
 
@@ -172,28 +188,13 @@ def stem_eligible(conv: nn.Conv2d, x_dtype=torch.bfloat16) -> bool:
             and 0 <= conv.padding[0] <= conv.kernel_size[0] // 2)
 
 
-class Conv2dStem(nn.Module):
-    """Drop-in for a stem_eligible nn.Conv2d, running the stem kernels.
-    Shares the conv's weight Parameter, so state_dict keys are unchanged."""
+class Conv2dStem(_NativeConv2d):
+    """Drop-in for a stem_eligible nn.Conv2d, running the stem kernels."""
 
-    def __init__(self, conv: nn.Conv2d):
-        super().__init__()
-        self.in_channels = conv.in_channels
-        self.out_channels = conv.out_channels
-        self.kernel_size = conv.kernel_size
-        self.stride = conv.stride[0]
-        self.padding = conv.padding[0]
-        self.weight = conv.weight
+    tag = "stem"
 
-    def forward(self, x):
-        if x.is_cuda and x.dtype == torch.bfloat16:
-            return conv2d_stem(x, self.weight, self.stride, self.padding)
-        return F.conv2d(x, self.weight, None, self.stride, self.padding)
-
-    def extra_repr(self):
-        return (f"{self.in_channels}, {self.out_channels}, "
-                f"k={self.kernel_size}, stride={self.stride}, "
-                f"pad={self.padding} [stem]")
+    def native(self, x):
+        return conv2d_stem(x, self.weight, self.stride, self.padding)
 
 
 def convert_convs(model: nn.Module, dtype=torch.bfloat16,

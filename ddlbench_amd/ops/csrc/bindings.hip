@@ -12,88 +12,9 @@
 #include <unordered_map>
 #include <vector>
 
-// ---- launcher declarations (defined in the .hip kernel files) ---------
-template <typename T>
-void launch_fused_sgd(uintptr_t*, uintptr_t*, uintptr_t*, const int64_t*,
-                      int, int64_t, float, float, float, int, hipStream_t);
-template <typename T>
-void launch_fused_adam(uintptr_t*, uintptr_t*, uintptr_t*, uintptr_t*,
-                       const int64_t*, int, int64_t, float, float, float,
-                       float, float, float, float, int, hipStream_t);
+#include "launchers.h"
 
-template <typename T>
-void launch_bn_stats(const T*, double*, int64_t, int64_t, int64_t, int64_t,
-                     int, hipStream_t);
-void set_bn_variant(int v);
-int64_t bn_reduce_gridS(int64_t N, int64_t C, int64_t HW, int nhwc,
-                        int elsize);
-void launch_bn_finalize(double*, float*, float*, float*, float*,
-                        int64_t, int64_t, double, float, float,
-                        hipStream_t);
-template <typename T>
-bool launch_bn_apply(const T*, const T*, T*, const float*, const float*,
-                     const float*, const float*, unsigned char*, int64_t,
-                     int64_t, int64_t, int, int, hipStream_t);
-template <typename T>
-void launch_bn_bwd_reduce(const T*, const T*, const T*, const float*,
-                          const float*, double*, const unsigned char*,
-                          int64_t, int64_t, int64_t, int64_t,
-                          int, int, hipStream_t);
-void launch_bn_bwd_finalize(double*, const float*, const float*,
-                            float*, float*, float*, int64_t, int64_t,
-                            double, int, hipStream_t);
-template <typename T>
-void launch_bn_bwd_dx(const T*, const T*, const T*, const float*,
-                      const float*, const float*, T*, T*,
-                      const unsigned char*, int64_t, int64_t,
-                      int64_t, int, int, hipStream_t);
-
-template <typename T>
-void launch_ce_fwd(const T*, const int64_t*, float*, float*, int64_t,
-                   int64_t, hipStream_t);
-template <typename T>
-void launch_ce_bwd(const T*, const int64_t*, const float*, const float*, T*,
-                   int64_t, int64_t, hipStream_t);
-
-void launch_conv_igemm(const void*, const void*, void*, const void*, int,
-                       int, int, int, int, int, int, int, int, int, int,
-                       int, hipStream_t);
-void launch_conv_wgrad(const void*, const void*, float*, float*, long,
-                       const void*, int,
-                       int, int, int, int, int, int, int, int, int, int,
-                       hipStream_t);
-
-void launch_conv_stem_fwd(const void*, const void*, void*, int, int, int,
-                          int, int, int, int, int, int, int, hipStream_t);
-void launch_conv_stem_wgrad(const void*, const void*, float*, float*, int,
-                            int, int, int, int, int, int, int, int, int,
-                            hipStream_t);
-int conv_stem_wgrad_chunks(int N, int OH, int OW, int K);
-
-void launch_maxpool_fwd(const void*, void*, unsigned char*, int64_t,
-                        int64_t, int, int, int, int, int, int, int,
-                        hipStream_t);
-void launch_maxpool_bwd(const void*, const unsigned char*, void*,
-                        int64_t, int64_t, int, int, int, int, int, int,
-                        int, hipStream_t);
-
-template <typename T>
-void launch_revert_varlen(const T*, T*, const int64_t*, int64_t, int64_t,
-                          int64_t, hipStream_t);
-void launch_varlen_mask(const int64_t*, uint8_t*, int64_t, int64_t,
-                        hipStream_t);
-
-template <typename T>
-void launch_dw3x3_fwd(const T*, const float*, T*, int64_t, int64_t, int64_t,
-                      int64_t, int64_t, int64_t, int, int, hipStream_t);
-template <typename T>
-void launch_dw3x3_bwd_dx(const T*, const float*, T*, int64_t, int64_t,
-                         int64_t, int64_t, int64_t, int64_t, int, int,
-                         hipStream_t);
-template <typename T>
-void launch_dw3x3_bwd_dw(const T*, const T*, double*, int64_t, int64_t,
-                         int64_t, int64_t, int64_t, int64_t, int, int,
-                         hipStream_t);
+using namespace ddlb;
 
 namespace {
 
@@ -115,37 +36,69 @@ T* dptr(const torch::Tensor& t) {
   return reinterpret_cast<T*>(t.data_ptr());
 }
 
-// Cached per-device 16-byte zero page for the conv kernels' padding
-// redirect (a fresh torch::zeros per call cost ~160 fill launches per
-// training step).
-torch::Tensor zero_page(const torch::Tensor& like) {
-  static std::unordered_map<int, torch::Tensor> zp;
-  const int dev = (int)like.get_device();
-  auto it = zp.find(dev);
-  if (it == zp.end()) {
-    zp[dev] = torch::zeros({16}, like.options().dtype(at::kBFloat16));
-    it = zp.find(dev);
-  }
-  return it->second;
+// Calls fn with a value-initialised element of x's dtype as a type tag:
+// __hip_bfloat16 for bf16 tensors, float otherwise.
+template <typename F>
+auto dispatch_f32_bf16(bool bf16, F&& fn) {
+  return bf16 ? fn(__hip_bfloat16{}) : fn(float{});
+}
+template <typename F>
+auto dispatch_f32_bf16(const torch::Tensor& x, F&& fn) {
+  return dispatch_f32_bf16(is_bf16(x), fn);
 }
 
-// Per-device BN reduction workspace: [S][2][C] double partial slabs.
+// Per-device cached workspace on `like`'s device: at least min_numel
+// elements of dtype, (re)allocated at max(min_numel, grow_floor) when
+// missing or too small. Contents are uninitialised unless `zeroed`.
+using WsCache = std::unordered_map<int, torch::Tensor>;
+torch::Tensor cached_ws(WsCache& cache, const torch::Tensor& like,
+                        at::ScalarType dtype, int64_t min_numel,
+                        int64_t grow_floor = 0, bool zeroed = false) {
+  torch::Tensor& t = cache[(int)like.get_device()];
+  if (!t.defined() || t.numel() < min_numel) {
+    const int64_t cap = std::max(min_numel, grow_floor);
+    const auto opt = like.options().dtype(dtype);
+    t = zeroed ? torch::zeros({cap}, opt) : torch::empty({cap}, opt);
+  }
+  return t;
+}
+
+// 16-element zero page for the conv kernels' padding redirect (a fresh
+// torch::zeros per call cost ~160 fill launches per training step).
+torch::Tensor zero_page(const torch::Tensor& like) {
+  static WsCache zp;
+  return cached_ws(zp, like, at::kBFloat16, 16, 0, /*zeroed=*/true);
+}
+
+// BN reduction workspace: [S][2][C] double partial slabs.
 // Reduce-style kernels write plain per-block stores and the finalize
 // kernels sum over S — no cross-block atomics (a C=64 layer at S~1500
 // slices serialized ~1500 f64 atomics per channel address), and no
 // zeroing (every slab slot is written every call).
 torch::Tensor bn_sums_workspace(const torch::Tensor& like, int64_t C,
                                 int64_t S) {
-  static std::unordered_map<int, torch::Tensor> ws;
-  const int dev = (int)like.get_device();
-  const int64_t need = 2 * C * S;
-  auto it = ws.find(dev);
-  if (it == ws.end() || it->second.numel() < need) {
-    const int64_t cap = std::max<int64_t>(need, 1 << 18);
-    ws[dev] = torch::empty({cap}, like.options().dtype(at::kDouble));
-    it = ws.find(dev);
-  }
-  return it->second;
+  static WsCache ws;
+  return cached_ws(ws, like, at::kDouble, 2 * C * S, 1 << 18);
+}
+
+// is_cuda + bf16 + channels_last, the operand contract of the conv and
+// pool bindings; `op` prefixes the dtype message
+void check_conv_operand(const torch::Tensor& t, const char* name,
+                        const char* op = "conv_igemm") {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16, op,
+              ": bf16 HIP tensors only");
+  TORCH_CHECK(t.is_contiguous(at::MemoryFormat::ChannelsLast), name,
+              " must be channels_last");
+}
+
+int conv_out_size(int64_t H, int64_t pad, int64_t R, int64_t stride) {
+  return (int)((H + 2 * pad - R) / stride + 1);
+}
+
+torch::Tensor empty_nhwc(const torch::Tensor& like, int64_t N, int64_t C,
+                         int64_t H, int64_t W) {
+  return torch::empty({N, C, H, W}, like.options().memory_format(
+                                        at::MemoryFormat::ChannelsLast));
 }
 
 }  // namespace
@@ -156,19 +109,13 @@ void fused_sgd(torch::Tensor ptr_params, torch::Tensor ptr_grads,
                double lr, double momentum, double weight_decay,
                bool first_step, bool bf16) {
   check_gpu_contig(ptr_params, "ptr_params");
-  auto s = cur_stream();
-  if (bf16)
-    launch_fused_sgd<__hip_bfloat16>(
+  dispatch_f32_bf16(bf16, [&](auto tag) {
+    launch_fused_sgd<decltype(tag)>(
         dptr<uintptr_t>(ptr_params), dptr<uintptr_t>(ptr_grads),
         dptr<uintptr_t>(ptr_moms), dptr<int64_t>(prefix),
         (int)ptr_params.numel(), total, (float)lr, (float)momentum,
-        (float)weight_decay, first_step, s);
-  else
-    launch_fused_sgd<float>(
-        dptr<uintptr_t>(ptr_params), dptr<uintptr_t>(ptr_grads),
-        dptr<uintptr_t>(ptr_moms), dptr<int64_t>(prefix),
-        (int)ptr_params.numel(), total, (float)lr, (float)momentum,
-        (float)weight_decay, first_step, s);
+        (float)weight_decay, first_step, cur_stream());
+  });
 }
 
 void fused_adam(torch::Tensor ptr_params, torch::Tensor ptr_grads,
@@ -178,21 +125,14 @@ void fused_adam(torch::Tensor ptr_params, torch::Tensor ptr_grads,
                 double weight_decay, double bc1, double bc2,
                 bool decoupled_wd, bool bf16) {
   check_gpu_contig(ptr_params, "ptr_params");
-  auto s = cur_stream();
-  if (bf16)
-    launch_fused_adam<__hip_bfloat16>(
+  dispatch_f32_bf16(bf16, [&](auto tag) {
+    launch_fused_adam<decltype(tag)>(
         dptr<uintptr_t>(ptr_params), dptr<uintptr_t>(ptr_grads),
         dptr<uintptr_t>(ptr_ms), dptr<uintptr_t>(ptr_vs),
         dptr<int64_t>(prefix), (int)ptr_params.numel(), total, (float)lr,
         (float)beta1, (float)beta2, (float)eps, (float)weight_decay,
-        (float)bc1, (float)bc2, decoupled_wd, s);
-  else
-    launch_fused_adam<float>(
-        dptr<uintptr_t>(ptr_params), dptr<uintptr_t>(ptr_grads),
-        dptr<uintptr_t>(ptr_ms), dptr<uintptr_t>(ptr_vs),
-        dptr<int64_t>(prefix), (int)ptr_params.numel(), total, (float)lr,
-        (float)beta1, (float)beta2, (float)eps, (float)weight_decay,
-        (float)bc1, (float)bc2, decoupled_wd, s);
+        (float)bc1, (float)bc2, decoupled_wd, cur_stream());
+  });
 }
 
 // ---- fused BN + act (+residual) ---------------------------------------
@@ -214,13 +154,11 @@ std::vector<torch::Tensor> bn_act_fwd(
     const int64_t S =
         bn_reduce_gridS(N, C, HW, nhwc, (int)x.element_size());
     torch::Tensor sums = bn_sums_workspace(x, C, S);
-    if (is_bf16(x))
-      launch_bn_stats<__hip_bfloat16>(dptr<__hip_bfloat16>(x),
-                                      dptr<double>(sums), N, C, HW, S,
-                                      nhwc, s);
-    else
-      launch_bn_stats<float>(dptr<float>(x), dptr<double>(sums), N, C, HW,
-                             S, nhwc, s);
+    dispatch_f32_bf16(x, [&](auto tag) {
+      using T = decltype(tag);
+      launch_bn_stats<T>(dptr<T>(x), dptr<double>(sums), N, C, HW, S, nhwc,
+                         s);
+    });
     launch_bn_finalize(
         dptr<double>(sums), dptr<float>(mean), dptr<float>(invstd),
         running_mean ? dptr<float>(*running_mean) : nullptr,
@@ -241,21 +179,16 @@ std::vector<torch::Tensor> bn_act_fwd(
       training && act != 0 && nhwc && is_bf16(x) && C % 8 == 0;
   if (want_mask)
     msk = torch::empty({total / 8}, x.options().dtype(at::kByte));
-  bool mask_written = false;
-  if (is_bf16(x))
-    mask_written = launch_bn_apply<__hip_bfloat16>(
-        dptr<__hip_bfloat16>(x),
-        res ? dptr<__hip_bfloat16>(*res) : nullptr, dptr<__hip_bfloat16>(y),
+  // want_mask is bf16-only, so the fp32 launch never gets a mask pointer
+  const bool mask_written = dispatch_f32_bf16(x, [&](auto tag) {
+    using T = decltype(tag);
+    return launch_bn_apply<T>(
+        dptr<T>(x), res ? dptr<T>(*res) : nullptr, dptr<T>(y),
         dptr<float>(mean), dptr<float>(invstd), dptr<float>(gamma),
         dptr<float>(beta),
         want_mask ? msk.data_ptr<unsigned char>() : nullptr,
         C, HW, total, (int)act, nhwc, s);
-  else
-    launch_bn_apply<float>(dptr<float>(x),
-                           res ? dptr<float>(*res) : nullptr, dptr<float>(y),
-                           dptr<float>(mean), dptr<float>(invstd),
-                           dptr<float>(gamma), dptr<float>(beta), nullptr,
-                           C, HW, total, (int)act, nhwc, s);
+  });
   if (mask_written) return {y, mean, invstd, msk};
   return {y, mean, invstd};
 }
@@ -285,42 +218,26 @@ std::vector<torch::Tensor> bn_act_bwd(torch::Tensor dy,
   const int64_t total = x.numel();
   const unsigned char* mp =
       msk ? msk->data_ptr<unsigned char>() : nullptr;
-  if (is_bf16(x)) {
-    TORCH_CHECK(mp || y_opt, "masked path needs the mask tensor");
-    const __hip_bfloat16* yp =
-        y_opt ? dptr<__hip_bfloat16>(*y_opt) : nullptr;
-    launch_bn_bwd_reduce<__hip_bfloat16>(
-        dptr<__hip_bfloat16>(dy), yp,
-        dptr<__hip_bfloat16>(x), dptr<float>(mean), dptr<float>(invstd),
-        dptr<double>(sums), mp, N, C, HW, S, (int)act, nhwc, s);
-    launch_bn_bwd_finalize(dptr<double>(sums), dptr<float>(gamma),
-                           dptr<float>(invstd), dptr<float>(dgamma),
-                           dptr<float>(dbeta), dptr<float>(k), C, S,
-                           (double)(N * HW), training, s);
-    launch_bn_bwd_dx<__hip_bfloat16>(
-        dptr<__hip_bfloat16>(dy), yp,
-        dptr<__hip_bfloat16>(x), dptr<float>(mean), dptr<float>(invstd),
-        dptr<float>(k), dptr<__hip_bfloat16>(dx),
-        need_dres ? dptr<__hip_bfloat16>(dres) : nullptr, mp, C, HW, total,
-        (int)act, nhwc, s);
-  } else {
+  // the fp32 kernels read y and never the mask
+  if (!is_bf16(x)) {
     TORCH_CHECK(y_opt, "fp32 backward needs y");
-    launch_bn_bwd_reduce<float>(dptr<float>(dy), dptr<float>(*y_opt),
-                                dptr<float>(x), dptr<float>(mean),
-                                dptr<float>(invstd), dptr<double>(sums),
-                                nullptr, N, C, HW, S, (int)act, nhwc, s);
+    mp = nullptr;
+  }
+  dispatch_f32_bf16(x, [&](auto tag) {
+    using T = decltype(tag);
+    const T* yp = y_opt ? dptr<T>(*y_opt) : nullptr;
+    launch_bn_bwd_reduce<T>(dptr<T>(dy), yp, dptr<T>(x), dptr<float>(mean),
+                            dptr<float>(invstd), dptr<double>(sums), mp, N,
+                            C, HW, S, (int)act, nhwc, s);
     launch_bn_bwd_finalize(dptr<double>(sums), dptr<float>(gamma),
                            dptr<float>(invstd), dptr<float>(dgamma),
                            dptr<float>(dbeta), dptr<float>(k), C, S,
                            (double)(N * HW), training, s);
-    launch_bn_bwd_dx<float>(dptr<float>(dy), dptr<float>(*y_opt),
-                            dptr<float>(x),
-                            dptr<float>(mean), dptr<float>(invstd),
-                            dptr<float>(k), dptr<float>(dx),
-                            need_dres ? dptr<float>(dres) : nullptr,
-                            nullptr, C, HW,
-                            total, (int)act, nhwc, s);
-  }
+    launch_bn_bwd_dx<T>(dptr<T>(dy), yp, dptr<T>(x), dptr<float>(mean),
+                        dptr<float>(invstd), dptr<float>(k), dptr<T>(dx),
+                        need_dres ? dptr<T>(dres) : nullptr, mp, C, HW,
+                        total, (int)act, nhwc, s);
+  });
   if (need_dres) return {dx, dgamma, dbeta, dres};
   return {dx, dgamma, dbeta};
 }
@@ -334,13 +251,11 @@ std::vector<torch::Tensor> ce_fwd(torch::Tensor logits,
   auto fopt = logits.options().dtype(at::kFloat);
   torch::Tensor lse = torch::empty({B}, fopt);
   torch::Tensor loss_sum = torch::zeros({1}, fopt);
-  if (is_bf16(logits))
-    launch_ce_fwd<__hip_bfloat16>(dptr<__hip_bfloat16>(logits),
-                                  dptr<int64_t>(target), dptr<float>(lse),
-                                  dptr<float>(loss_sum), B, K, s);
-  else
-    launch_ce_fwd<float>(dptr<float>(logits), dptr<int64_t>(target),
-                         dptr<float>(lse), dptr<float>(loss_sum), B, K, s);
+  dispatch_f32_bf16(logits, [&](auto tag) {
+    using T = decltype(tag);
+    launch_ce_fwd<T>(dptr<T>(logits), dptr<int64_t>(target),
+                     dptr<float>(lse), dptr<float>(loss_sum), B, K, s);
+  });
   return {loss_sum, lse};
 }
 
@@ -349,15 +264,12 @@ torch::Tensor ce_bwd(torch::Tensor logits, torch::Tensor target,
   const int64_t B = logits.size(0), K = logits.size(1);
   auto s = cur_stream();
   torch::Tensor dx = torch::empty_like(logits);
-  if (is_bf16(logits))
-    launch_ce_bwd<__hip_bfloat16>(dptr<__hip_bfloat16>(logits),
-                                  dptr<int64_t>(target), dptr<float>(lse),
-                                  dptr<float>(gscale),
-                                  dptr<__hip_bfloat16>(dx), B, K, s);
-  else
-    launch_ce_bwd<float>(dptr<float>(logits), dptr<int64_t>(target),
-                         dptr<float>(lse), dptr<float>(gscale),
-                         dptr<float>(dx), B, K, s);
+  dispatch_f32_bf16(logits, [&](auto tag) {
+    using T = decltype(tag);
+    launch_ce_bwd<T>(dptr<T>(logits), dptr<int64_t>(target),
+                     dptr<float>(lse), dptr<float>(gscale), dptr<T>(dx), B,
+                     K, s);
+  });
   return dx;
 }
 
@@ -366,25 +278,17 @@ torch::Tensor ce_bwd(torch::Tensor logits, torch::Tensor target,
 // channels_last memory (= (K,R,S,C) image). Returns channels_last y.
 torch::Tensor conv_igemm_fwd(torch::Tensor x, torch::Tensor w,
                              int64_t stride, int64_t pad) {
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16,
-              "conv_igemm: bf16 HIP tensors only");
-  TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "x must be channels_last");
-  TORCH_CHECK(w.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "w must be channels_last");
+  check_conv_operand(x, "x", "conv_igemm");
+  check_conv_operand(w, "w", "conv_igemm");
   const int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   const int K = w.size(0), R = w.size(2), S = w.size(3);
   TORCH_CHECK(C % 8 == 0, "conv_igemm fwd needs C % 8 == 0");
-  const int OH = (H + 2 * (int)pad - R) / (int)stride + 1;
-  const int OW = (W + 2 * (int)pad - S) / (int)stride + 1;
-  auto y = torch::empty({N, K, OH, OW},
-                        x.options().memory_format(
-                            at::MemoryFormat::ChannelsLast));
-  auto zero = zero_page(x);
+  const int OH = conv_out_size(H, pad, R, stride);
+  const int OW = conv_out_size(W, pad, S, stride);
+  auto y = empty_nhwc(x, N, K, OH, OW);
   launch_conv_igemm(x.data_ptr(), w.data_ptr(), y.data_ptr(),
-                    zero.data_ptr(), N, H, W, C, K, OH, OW, R, S,
-                    (int)stride, (int)pad, /*dgrad=*/0,
-                    cur_stream());
+                    zero_page(x).data_ptr(), N, H, W, C, K, OH, OW, R, S,
+                    (int)stride, (int)pad, /*dgrad=*/0, cur_stream());
   return y;
 }
 
@@ -393,10 +297,7 @@ torch::Tensor conv_igemm_fwd(torch::Tensor x, torch::Tensor w,
 torch::Tensor conv_igemm_dgrad(torch::Tensor dy, torch::Tensor w_perm,
                                int64_t N, int64_t C, int64_t H, int64_t W,
                                int64_t stride, int64_t pad) {
-  TORCH_CHECK(dy.is_cuda() && dy.scalar_type() == at::kBFloat16,
-              "conv_igemm: bf16 HIP tensors only");
-  TORCH_CHECK(dy.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "dy must be channels_last");
+  check_conv_operand(dy, "dy", "conv_igemm");
   TORCH_CHECK(w_perm.is_contiguous(), "w_perm must be contiguous");
   const int K = dy.size(1), OH = dy.size(2), OW = dy.size(3);
   const int R = w_perm.size(1), S = w_perm.size(2);
@@ -405,15 +306,12 @@ torch::Tensor conv_igemm_dgrad(torch::Tensor dy, torch::Tensor w_perm,
   // reaches — those dx entries must be zeros, so zero-init in that case
   // (zero_() after empty: torch::zeros does not honour the
   // channels_last memory_format request)
-  auto dx = torch::empty({N, C, H, W},
-                         dy.options().memory_format(
-                             at::MemoryFormat::ChannelsLast));
+  auto dx = empty_nhwc(dy, N, C, H, W);
   if (stride == 2 && (R == 1 || S == 1)) dx.zero_();
-  auto zero = zero_page(dy);
   launch_conv_igemm(dy.data_ptr(), w_perm.data_ptr(), dx.data_ptr(),
-                    zero.data_ptr(), (int)N, (int)H, (int)W, (int)C, K,
-                    OH, OW, R, S, (int)stride, (int)pad, /*dgrad=*/1,
-                    cur_stream());
+                    zero_page(dy).data_ptr(), (int)N, (int)H, (int)W,
+                    (int)C, K, OH, OW, R, S, (int)stride, (int)pad,
+                    /*dgrad=*/1, cur_stream());
   return dx;
 }
 
@@ -423,34 +321,22 @@ torch::Tensor conv_igemm_dgrad(torch::Tensor dy, torch::Tensor w_perm,
 torch::Tensor conv_igemm_wgrad(torch::Tensor x, torch::Tensor dy,
                                int64_t R, int64_t S, int64_t stride,
                                int64_t pad) {
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16,
-              "conv_wgrad: bf16 HIP tensors only");
-  TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "x must be channels_last");
-  TORCH_CHECK(dy.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "dy must be channels_last");
+  check_conv_operand(x, "x", "conv_wgrad");
+  check_conv_operand(dy, "dy", "conv_wgrad");
   const int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   const int K = dy.size(1), OH = dy.size(2), OW = dy.size(3);
   TORCH_CHECK(C % 8 == 0 && K % 8 == 0,
               "conv_wgrad needs C %% 8 == 0 and K %% 8 == 0");
   auto dw = torch::empty({K, R * S * C},
                          x.options().dtype(at::kFloat));
-  auto zero = zero_page(x);
-  // split-P partial-slab workspace (cached per device, 32 MB fp32)
-  static std::unordered_map<int, torch::Tensor> wgws;
-  const int devi = (int)x.get_device();
-  auto wit = wgws.find(devi);
-  if (wit == wgws.end()) {
-    wgws[devi] = torch::empty({8 << 20},
-                              x.options().dtype(at::kFloat));
-    wit = wgws.find(devi);
-  }
-  launch_conv_wgrad(x.data_ptr(), dy.data_ptr(),
-                    dw.data_ptr<float>(), wit->second.data_ptr<float>(),
-                    (long)wit->second.numel(), zero.data_ptr(),
-                    N, H, W, C, K,
-                    OH, OW, (int)R, (int)S, (int)stride, (int)pad,
-                    cur_stream());
+  // split-P partial-slab workspace: a fixed 8M floats (32 MB), the
+  // launcher caps its split to fit
+  static WsCache wgws;
+  auto part = cached_ws(wgws, x, at::kFloat, 8 << 20);
+  launch_conv_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr<float>(),
+                    part.data_ptr<float>(), (long)part.numel(),
+                    zero_page(x).data_ptr(), N, H, W, C, K, OH, OW, (int)R,
+                    (int)S, (int)stride, (int)pad, cur_stream());
   return dw;
 }
 
@@ -472,25 +358,18 @@ static void check_stem_shape(int64_t C, int64_t K, int64_t R, int64_t S,
 // row-major memory). Returns channels_last y.
 torch::Tensor conv_stem_fwd(torch::Tensor x, torch::Tensor w,
                             int64_t stride, int64_t pad) {
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 &&
-                  w.is_cuda() && w.scalar_type() == at::kBFloat16,
-              "conv_stem: bf16 HIP tensors only");
   TORCH_CHECK(x.dim() == 4 && w.dim() == 4, "conv_stem: 4-D tensors only");
-  TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "x must be channels_last");
-  TORCH_CHECK(w.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "w must be channels_last");
+  check_conv_operand(x, "x", "conv_stem");
+  check_conv_operand(w, "w", "conv_stem");
   const int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   const int K = w.size(0), R = w.size(2), S = w.size(3);
   TORCH_CHECK(w.size(1) == C, "conv_stem: weight C mismatch");
   check_stem_shape(C, K, R, S, stride, pad);
-  const int OH = (H + 2 * (int)pad - R) / (int)stride + 1;
-  const int OW = (W + 2 * (int)pad - S) / (int)stride + 1;
+  const int OH = conv_out_size(H, pad, R, stride);
+  const int OW = conv_out_size(W, pad, S, stride);
   TORCH_CHECK(N >= 1 && H + 2 * pad >= R && W + 2 * pad >= S,
               "conv_stem: empty output");
-  auto y = torch::empty({N, K, OH, OW},
-                        x.options().memory_format(
-                            at::MemoryFormat::ChannelsLast));
+  auto y = empty_nhwc(x, N, K, OH, OW);
   launch_conv_stem_fwd(x.data_ptr(), w.data_ptr(), y.data_ptr(), N, H, W, C,
                        K, OH, OW, R, (int)stride, (int)pad, cur_stream());
   return y;
@@ -500,36 +379,26 @@ torch::Tensor conv_stem_fwd(torch::Tensor x, torch::Tensor w,
 // dw in (K, R*S*C) memory — the conv_igemm_wgrad convention.
 torch::Tensor conv_stem_wgrad(torch::Tensor x, torch::Tensor dy, int64_t R,
                               int64_t S, int64_t stride, int64_t pad) {
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 &&
-                  dy.is_cuda() && dy.scalar_type() == at::kBFloat16,
-              "conv_stem: bf16 HIP tensors only");
   TORCH_CHECK(x.dim() == 4 && dy.dim() == 4, "conv_stem: 4-D tensors only");
-  TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "x must be channels_last");
-  TORCH_CHECK(dy.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "dy must be channels_last");
+  check_conv_operand(x, "x", "conv_stem");
+  check_conv_operand(dy, "dy", "conv_stem");
   const int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   const int K = dy.size(1), OH = dy.size(2), OW = dy.size(3);
   check_stem_shape(C, K, R, S, stride, pad);
   TORCH_CHECK(N >= 1 && dy.size(0) == N && OH >= 1 && OW >= 1 &&
-                  OH == (H + 2 * pad - R) / stride + 1 &&
-                  OW == (W + 2 * pad - S) / stride + 1,
+                  OH == conv_out_size(H, pad, R, stride) &&
+                  OW == conv_out_size(W, pad, S, stride),
               "conv_stem: dy shape does not match x");
   const int64_t total = (int64_t)K * R * S * C;
   auto dw = torch::empty({K, R * S * C}, x.options().dtype(at::kFloat));
-  // per-block partial slabs (cached per device, grown on demand); every
-  // slab element the combine reads is written by the same call
-  static std::unordered_map<int, torch::Tensor> stws;
-  const int devi = (int)x.get_device();
-  const int64_t need = total * conv_stem_wgrad_chunks(N, OH, OW, K);
-  auto wit = stws.find(devi);
-  if (wit == stws.end() || wit->second.numel() < need) {
-    stws[devi] = torch::empty({need}, x.options().dtype(at::kFloat));
-    wit = stws.find(devi);
-  }
+  // per-block partial slabs, grown to need; every slab element the
+  // combine reads is written by the same call
+  static WsCache stws;
+  auto part = cached_ws(stws, x, at::kFloat,
+                        total * conv_stem_wgrad_chunks(N, OH, OW, K));
   launch_conv_stem_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr<float>(),
-                         wit->second.data_ptr<float>(), N, H, W, C, K, OH,
-                         OW, (int)R, (int)stride, (int)pad, cur_stream());
+                         part.data_ptr<float>(), N, H, W, C, K, OH, OW,
+                         (int)R, (int)stride, (int)pad, cur_stream());
   return dw;
 }
 
@@ -586,13 +455,11 @@ torch::Tensor dw3x3_fwd(torch::Tensor x, torch::Tensor w, int64_t stride,
       ? torch::empty({N, C, OH, OW}, x.options().memory_format(
             at::MemoryFormat::ChannelsLast))
       : torch::empty({N, C, OH, OW}, x.options());
-  if (is_bf16(x))
-    launch_dw3x3_fwd<__hip_bfloat16>(dptr<__hip_bfloat16>(x), dptr<float>(w),
-                                     dptr<__hip_bfloat16>(y), N, C, H, W, OH,
-                                     OW, (int)stride, nhwc, s);
-  else
-    launch_dw3x3_fwd<float>(dptr<float>(x), dptr<float>(w), dptr<float>(y),
-                            N, C, H, W, OH, OW, (int)stride, nhwc, s);
+  dispatch_f32_bf16(x, [&](auto tag) {
+    using T = decltype(tag);
+    launch_dw3x3_fwd<T>(dptr<T>(x), dptr<float>(w), dptr<T>(y), N, C, H, W,
+                        OH, OW, (int)stride, nhwc, s);
+  });
   return y;
 }
 
@@ -606,26 +473,19 @@ std::vector<torch::Tensor> dw3x3_bwd(torch::Tensor x, torch::Tensor w,
   torch::Tensor dx, dwt;
   if (need_dx) {
     dx = torch::empty_like(x);
-    if (is_bf16(x))
-      launch_dw3x3_bwd_dx<__hip_bfloat16>(
-          dptr<__hip_bfloat16>(dy), dptr<float>(w), dptr<__hip_bfloat16>(dx),
-          N, C, H, W, OH, OW, (int)stride, nhwc, s);
-    else
-      launch_dw3x3_bwd_dx<float>(dptr<float>(dy), dptr<float>(w),
-                                 dptr<float>(dx), N, C, H, W, OH, OW,
-                                 (int)stride, nhwc, s);
+    dispatch_f32_bf16(x, [&](auto tag) {
+      using T = decltype(tag);
+      launch_dw3x3_bwd_dx<T>(dptr<T>(dy), dptr<float>(w), dptr<T>(dx), N, C,
+                             H, W, OH, OW, (int)stride, nhwc, s);
+    });
   }
   if (need_dw) {
     torch::Tensor acc = torch::zeros({C * 9}, x.options().dtype(at::kDouble));
-    if (is_bf16(x))
-      launch_dw3x3_bwd_dw<__hip_bfloat16>(dptr<__hip_bfloat16>(x),
-                                          dptr<__hip_bfloat16>(dy),
-                                          dptr<double>(acc), N, C, H, W, OH,
-                                          OW, (int)stride, nhwc, s);
-    else
-      launch_dw3x3_bwd_dw<float>(dptr<float>(x), dptr<float>(dy),
-                                 dptr<double>(acc), N, C, H, W, OH, OW,
-                                 (int)stride, nhwc, s);
+    dispatch_f32_bf16(x, [&](auto tag) {
+      using T = decltype(tag);
+      launch_dw3x3_bwd_dw<T>(dptr<T>(x), dptr<T>(dy), dptr<double>(acc), N,
+                             C, H, W, OH, OW, (int)stride, nhwc, s);
+    });
     dwt = acc.to(at::kFloat).view({C, 1, 3, 3});
   }
   return {dx, dwt};
@@ -639,13 +499,11 @@ torch::Tensor revert_varlen(torch::Tensor x, torch::Tensor lengths) {
   const int64_t T = x.size(0), B = x.size(1), F = x.size(2);
   auto out = torch::empty_like(x);
   auto s = cur_stream();
-  if (is_bf16(x))
-    launch_revert_varlen<__hip_bfloat16>(
-        dptr<__hip_bfloat16>(x), dptr<__hip_bfloat16>(out),
-        dptr<int64_t>(lengths), T, B, F, s);
-  else
-    launch_revert_varlen<float>(dptr<float>(x), dptr<float>(out),
-                                dptr<int64_t>(lengths), T, B, F, s);
+  dispatch_f32_bf16(x, [&](auto tag) {
+    using E = decltype(tag);
+    launch_revert_varlen<E>(dptr<E>(x), dptr<E>(out),
+                            dptr<int64_t>(lengths), T, B, F, s);
+  });
   return out;
 }
 

@@ -14,6 +14,7 @@
 // Activation codes: 0 = identity, 1 = relu, 2 = relu6.
 
 #include "common.h"
+#include "launchers.h"
 #include <stdint.h>
 #include <stdexcept>
 #include <string>
@@ -39,7 +40,7 @@ template <int ACT> DEV float act_mask(float y) {
 // 0 = auto, 1 = scalar-group reductions + grid-stride vector apply,
 // 2 = vector reductions + fixed-channel apply
 int g_bn_variant = 0;
-void set_bn_variant(int v) { g_bn_variant = v; }
+void ddlb::set_bn_variant(int v) { g_bn_variant = v; }
 
 // ---- stats: per-channel sum / sumsq over N*H*W ------------------------
 // grid = (C, S): block (c, s) covers slice s of channel c's N*HW space.
@@ -787,16 +788,17 @@ static BnGeom bn_reduce_geom(int64_t rows, int64_t C, int elsize) {
   return g;
 }
 
-int64_t bn_reduce_gridS(int64_t N, int64_t C, int64_t HW, int nhwc,
-                        int elsize) {
+int64_t ddlb::bn_reduce_gridS(int64_t N, int64_t C, int64_t HW, int nhwc,
+                              int elsize) {
   if (nhwc) return bn_reduce_geom(N * HW, C, elsize).S;
   int64_t S = i64min((N * HW + 255) / 256, i64max(2048 / C, 1));
   return i64max(S, 1);
 }
 
 template <typename T>
-void launch_bn_stats(const T* x, double* sums, int64_t N, int64_t C,
-                     int64_t HW, int64_t S, int nhwc, hipStream_t stream) {
+void ddlb::launch_bn_stats(const T* x, double* sums, int64_t N, int64_t C,
+                           int64_t HW, int64_t S, int nhwc,
+                           hipStream_t stream) {
   const int block = 256;
   if (nhwc) {
     const int64_t rows = N * HW;
@@ -823,10 +825,10 @@ void launch_bn_stats(const T* x, double* sums, int64_t N, int64_t C,
   HIP_CHECK_LAST();
 }
 
-void launch_bn_finalize(double* sums, float* mean, float* invstd,
-                        float* rm, float* rv, int64_t C, int64_t S,
-                        double count,
-                        float eps, float momentum, hipStream_t stream) {
+void ddlb::launch_bn_finalize(double* sums, float* mean, float* invstd,
+                              float* rm, float* rv, int64_t C, int64_t S,
+                              double count, float eps, float momentum,
+                              hipStream_t stream) {
   const int block = 1024;
   hipLaunchKernelGGL(bn_finalize_kernel, dim3((unsigned)C),
                      dim3(block), 0, stream, sums, mean, invstd, rm, rv, C,
@@ -835,11 +837,11 @@ void launch_bn_finalize(double* sums, float* mean, float* invstd,
 }
 
 template <typename T>
-bool launch_bn_apply(const T* x, const T* res, T* y, const float* mean,
-                     const float* invstd, const float* gamma,
-                     const float* beta, unsigned char* msk, int64_t C,
-                     int64_t HW, int64_t total,
-                     int act, int nhwc, hipStream_t stream) {
+bool ddlb::launch_bn_apply(const T* x, const T* res, T* y, const float* mean,
+                           const float* invstd, const float* gamma,
+                           const float* beta, unsigned char* msk, int64_t C,
+                           int64_t HW, int64_t total, int act, int nhwc,
+                           hipStream_t stream) {
   const int block = 256;
   const int64_t cdiv = nhwc ? 1 : HW;
   const bool vec8ok = (total % 8 == 0) &&
@@ -905,11 +907,11 @@ bool launch_bn_apply(const T* x, const T* res, T* y, const float* mean,
 }
 
 template <typename T>
-void launch_bn_bwd_reduce(const T* dy, const T* y, const T* x,
-                          const float* mean, const float* invstd,
-                          double* sums, const unsigned char* msk,
-                          int64_t N, int64_t C, int64_t HW, int64_t S,
-                          int act, int nhwc, hipStream_t stream) {
+void ddlb::launch_bn_bwd_reduce(const T* dy, const T* y, const T* x,
+                                const float* mean, const float* invstd,
+                                double* sums, const unsigned char* msk,
+                                int64_t N, int64_t C, int64_t HW, int64_t S,
+                                int act, int nhwc, hipStream_t stream) {
   const int block = 256;
   if (nhwc) {
     const int64_t rows = N * HW;
@@ -949,10 +951,11 @@ void launch_bn_bwd_reduce(const T* dy, const T* y, const T* x,
   HIP_CHECK_LAST();
 }
 
-void launch_bn_bwd_finalize(double* sums, const float* gamma,
-                            const float* invstd, float* dgamma, float* dbeta,
-                            float* k, int64_t C, int64_t S, double count,
-                            int training, hipStream_t stream) {
+void ddlb::launch_bn_bwd_finalize(double* sums, const float* gamma,
+                                  const float* invstd, float* dgamma,
+                                  float* dbeta, float* k, int64_t C, int64_t S,
+                                  double count, int training,
+                                  hipStream_t stream) {
   const int block = 1024;
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)C),
                      dim3(block), 0, stream, sums, gamma, invstd, dgamma,
@@ -961,11 +964,12 @@ void launch_bn_bwd_finalize(double* sums, const float* gamma,
 }
 
 template <typename T>
-void launch_bn_bwd_dx(const T* dy, const T* y, const T* x, const float* mean,
-                      const float* invstd, const float* k, T* dx, T* dres,
-                      const unsigned char* msk,
-                      int64_t C, int64_t HW, int64_t total, int act,
-                      int nhwc, hipStream_t stream) {
+void ddlb::launch_bn_bwd_dx(const T* dy, const T* y, const T* x,
+                            const float* mean, const float* invstd,
+                            const float* k, T* dx, T* dres,
+                            const unsigned char* msk, int64_t C, int64_t HW,
+                            int64_t total, int act, int nhwc,
+                            hipStream_t stream) {
   const int block = 256;
   const int64_t cdiv = nhwc ? 1 : HW;
   const bool vec8ok = (total % 8 == 0) &&
@@ -1037,23 +1041,21 @@ void launch_bn_bwd_dx(const T* dy, const T* y, const T* x, const float* mean,
 }
 
 #define INSTANTIATE(T)                                                        \
-  template void launch_bn_stats<T>(const T*, double*, int64_t, int64_t,       \
-                                   int64_t, int64_t, int, hipStream_t);       \
-  template bool launch_bn_apply<T>(const T*, const T*, T*, const float*,      \
-                                   const float*, const float*, const float*,  \
-                                   unsigned char*,                            \
-                                   int64_t, int64_t, int64_t, int, int,       \
-                                   hipStream_t);                              \
-  template void launch_bn_bwd_reduce<T>(const T*, const T*, const T*,         \
-                                        const float*, const float*, double*,  \
-                                        const unsigned char*,                 \
-                                        int64_t, int64_t, int64_t, int64_t,   \
-                                        int, int, hipStream_t);               \
-  template void launch_bn_bwd_dx<T>(const T*, const T*, const T*,             \
-                                    const float*, const float*, const float*, \
-                                    T*, T*, const unsigned char*,             \
-                                    int64_t, int64_t, int64_t, int,           \
-                                    int, hipStream_t);
+  template void ddlb::launch_bn_stats<T>(                                     \
+      const T*, double*, int64_t, int64_t, int64_t, int64_t, int,             \
+      hipStream_t);                                                           \
+  template bool ddlb::launch_bn_apply<T>(                                     \
+      const T*, const T*, T*, const float*, const float*, const float*,       \
+      const float*, unsigned char*, int64_t, int64_t, int64_t, int, int,      \
+      hipStream_t);                                                           \
+  template void ddlb::launch_bn_bwd_reduce<T>(                                \
+      const T*, const T*, const T*, const float*, const float*, double*,      \
+      const unsigned char*, int64_t, int64_t, int64_t, int64_t, int, int,     \
+      hipStream_t);                                                           \
+  template void ddlb::launch_bn_bwd_dx<T>(                                    \
+      const T*, const T*, const T*, const float*, const float*, const float*, \
+      T*, T*, const unsigned char*, int64_t, int64_t, int64_t, int, int,      \
+      hipStream_t);
 
 INSTANTIATE(float)
 INSTANTIATE(__hip_bfloat16)

@@ -26,21 +26,18 @@
 // crosses an (r,s) boundary.
 
 #include "conv_igemm.h"
+#include "launchers.h"
 #include <stdint.h>
 #include <stdexcept>
 #include <stdlib.h>
 #include <string>
 
 using bf16 = conv_bf16;
-typedef __attribute__((ext_vector_type(8))) short bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 #define BM 128
 #define BN 128
 #define BK 64
 #define THREADS 256
-
-using RowCoords = ConvRowCoords;
 
 // ---- chunk -> global address generators -------------------------------
 // A-chunk: logical (row=m in [0,BM), cg in [0,8)) of the current K-step.
@@ -54,12 +51,7 @@ using RowCoords = ConvRowCoords;
 // staging slot (conv_a_row_coords) and only the (r, s, c/k) part runs
 // per step (a_step_addr).
 template <int MODE>
-DEV RowCoords a_row_coords(const ConvParams& p, long m) {
-  return conv_a_row_coords<MODE>(p, m);
-}
-
-template <int MODE>
-DEV const bf16* a_step_addr(const ConvParams& p, const RowCoords& rc,
+DEV const bf16* a_step_addr(const ConvParams& p, const ConvRowCoords& rc,
                             long kkg) {
   if (!rc.valid) return p.zero;
   if (MODE == 0) {
@@ -137,15 +129,7 @@ void conv_igemm_kernel(ConvParams p) {
   const int wid = tid >> 6;
 
   const int nbn = (int)((p.Nd + BN_ - 1) / BN_);
-  int block = blockIdx.x;
-  // XCD-aware swizzle: contiguous chunks per XCD (bijective form)
-  {
-    const int nwg = gridDim.x;
-    const int q = nwg / 8, rmd = nwg % 8;
-    const int xcd = block % 8, idx = block / 8;
-    block = (xcd < rmd ? xcd * (q + 1) : rmd * (q + 1) + (xcd - rmd) * q)
-            + idx;
-  }
+  const int block = xcd_remap(blockIdx.x, gridDim.x);
   const long bm = (long)(block / nbn) * BM_;
   const long bn = (long)(block % nbn) * BN_;
 
@@ -154,13 +138,13 @@ void conv_igemm_kernel(ConvParams p) {
   // ---- staging slots: slot ca -> (row = ca>>3, stored cg = ca&7),
   // holding source logical cg = (ca&7) ^ (row&7)
   int a_cg[CA], b_row[CB], b_cg[CB];
-  RowCoords a_rc[CA];
+  ConvRowCoords a_rc[CA];
 #pragma unroll
   for (int l = 0; l < CA; ++l) {
     const int ca = l * THREADS + tid;
     const int arow = ca >> 3;
     a_cg[l] = (ca & 7) ^ (arow & 7);
-    a_rc[l] = a_row_coords<MODE>(p, bm + arow);
+    a_rc[l] = conv_a_row_coords<MODE>(p, bm + arow);
   }
 #pragma unroll
   for (int l = 0; l < CB; ++l) {
@@ -179,19 +163,13 @@ void conv_igemm_kernel(ConvParams p) {
       const bf16* src = a_step_addr<MODE>(p, a_rc[l],
                                           kkga < p.Kd ? kkga : 0);
       if (kkga >= p.Kd) src = p.zero;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)src,
-          (__attribute__((address_space(3))) void*)(la +
-              (l * THREADS + tid) * 8), 16, 0, 0);
+      glds16(src, la + (l * THREADS + tid) * 8);
     }
 #pragma unroll
     for (int l = 0; l < CB; ++l) {
       const bf16* src = b_chunk_addr<MODE>(p, bn + b_row[l],
                                            kk0 + b_cg[l] * 8);
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)src,
-          (__attribute__((address_space(3))) void*)(lb +
-              (l * THREADS + tid) * 8), 16, 0, 0);
+      glds16(src, lb + (l * THREADS + tid) * 8);
     }
   };
 
@@ -214,7 +192,7 @@ void conv_igemm_kernel(ConvParams p) {
       acc[i][j] = {0.f, 0.f, 0.f, 0.f};
 
   stage(0, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vmcnt<0>();
   __syncthreads();
 
   int cur = 0;
@@ -240,7 +218,7 @@ void conv_igemm_kernel(ConvParams p) {
               af[mf], bfr[nf], acc[mf][nf], 0, 0, 0);
       __builtin_amdgcn_s_setprio(0);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __syncthreads();
     cur ^= 1;
   }
@@ -252,16 +230,8 @@ void conv_igemm_kernel(ConvParams p) {
     for (int reg = 0; reg < 4; ++reg) {
       const long row = bm + wm + mf * 16 + fk * 4 + reg;
       if (row >= p.M) continue;
-      long out_row = row;
-      if (MODE == 2) {
-        // class row -> scattered dx pixel (n, 2*ii+a, 2*jj+b)
-        const int hw = p.nh * p.nw;
-        const int n = (int)(row / hw);
-        const int rem = (int)(row - (long)n * hw);
-        const int ii = rem / p.nw, jj = rem - (rem / p.nw) * p.nw;
-        out_row = ((long)n * p.H + 2 * ii + p.cls_a) * p.W
-                  + 2 * jj + p.cls_b;
-      }
+      // class row -> scattered dx pixel
+      const long out_row = (MODE == 2) ? conv_class_dx_row(p, row) : row;
 #pragma unroll
       for (int nf = 0; nf < NF; ++nf) {
         const long col = bn + wn + nf * 16 + fr;
@@ -273,10 +243,10 @@ void conv_igemm_kernel(ConvParams p) {
 }
 
 // ---- launchers --------------------------------------------------------
-void launch_conv_igemm(const void* a, const void* b, void* out,
-                       const void* zero, int N, int H, int W, int Cin,
-                       int K, int OH, int OW, int R, int S, int stride,
-                       int pad, int dgrad, hipStream_t stream) {
+void ddlb::launch_conv_igemm(const void* a, const void* b, void* out,
+                             const void* zero, int N, int H, int W, int Cin,
+                             int K, int OH, int OW, int R, int S, int stride,
+                             int pad, int dgrad, hipStream_t stream) {
   ConvParams p;
   p.a = (const bf16*)a;
   p.b = (const bf16*)b;

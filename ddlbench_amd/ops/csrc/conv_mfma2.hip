@@ -1,21 +1,22 @@
 // Deep-pipelined NHWC implicit-GEMM convolution on MFMA (gfx950, bf16).
 //
 // Second-generation structure for the conv core the reference gets from
-// cuDNN: the 256-row counted-vmcnt schedule from the
-// CDNA4 guide's 8-phase GEMM template (cdna_hip_programming.md §5),
-// adapted to implicit-GEMM staging:
+// cuDNN: the counted-vmcnt schedule of the CDNA4
+// guide's deep-pipelined GEMM (cdna_hip_programming.md §5), adapted to
+// implicit-GEMM staging:
 //
-//   * 256xBN block tile, BK=64, 8 waves (512 threads), 2 K-tile LDS
+//   * BMxBN block tile, BK=64, 8 waves (512 threads), 2 K-tile LDS
 //     double buffer staged entirely by 16-byte global_load_lds.
-//   * Each K-tile is computed in 4 phases (m-half x k-half); each phase
-//     {ds_read fragment subtile; issue ONE half-slot prefetch (glds);
-//      raw s_barrier; MFMA cluster under s_setprio(1); raw s_barrier}.
-//   * vmcnt is COUNTED, never drained mid-loop: one s_waitcnt
-//     vmcnt(GA+GB) per k-half boundary leaves the two most recent
-//     half-slot prefetches in flight across the barriers (~2 phases
-//     ~1100 cycles of slack > the ~900-cycle HBM latency). Raw
-//     s_barrier (not __syncthreads) so the barrier itself never drains
-//     the glds queue (the documented -16..-20% trap).
+//   * Each K-tile is computed in 2 phases, one per k-half, each over the
+//     wave's full M extent:
+//     {ds_read the A and B fragments; issue the next tile's prefetch
+//      (glds) for the same k-half; raw s_barrier; MFMA cluster under
+//      s_setprio(1); counted s_waitcnt; raw s_barrier}.
+//   * vmcnt is COUNTED, never drained mid-loop: the wait that ends a
+//     phase allows exactly the prefetch issued in that phase to stay in
+//     flight, so every load has one full phase of MFMA work to land
+//     behind. Raw s_barrier (not __syncthreads) so the barrier itself
+//     never drains the glds queue (the documented -16..-20% trap).
 //   * LDS layout: per (buffer, k-half) a [rows][32] bf16 slot; the
 //     16-byte chunk at (row, slot s) holds logical k-chunk
 //     cg = s ^ sigma((row>>2)&3) with sigma = [0,2,3,1] — derived from
@@ -30,10 +31,11 @@
 //     (r,s,c)-cursor advances by +32 with carries per stage call — no
 //     divmod in the K-loop.
 //
-// Variants: BN=256 (waves 2x4, wave tile 128x64, 16 MFMA/phase,
-// 128 KiB LDS) for Nd>=192; BN=128 (wave tile 128x32, 8 MFMA/phase,
-// 96 KiB LDS) for Nd>=96. Narrower Nd falls back to conv_mfma.hip's
-// 128-tile structure (launcher returns false).
+// Tiles (all 8 waves, 2 blocks/CU): 128x128 (waves 2x4, wave tile
+// 64x32, 8 MFMA/phase, 64 KiB LDS) for Nd >= 96; 256x64 (waves 4x2,
+// wave tile 64x32, combined-B staging, 80 KiB LDS) for Nd in [48, 96).
+// Narrower Nd falls back to conv_mfma.hip's 128-tile structure
+// (launcher returns false).
 
 #include "conv_igemm.h"
 #include <stdint.h>
@@ -41,40 +43,18 @@
 #include <string>
 
 using bf16 = conv_bf16;
-typedef __attribute__((ext_vector_type(8))) short bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
-#define BM2 256
 #define BK2 64
 #define THREADS2 512
 
 namespace {
 
-template <int N> DEV void wait_vmcnt() {
-  static_assert(N >= 0 && N <= 8, "unsupported vmcnt");
-  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  else if constexpr (N == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-  else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-  else if constexpr (N == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-  else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  else if constexpr (N == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-  else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  else if constexpr (N == 7) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-}
-
-DEV void glds16(const bf16* src, bf16* dst) {
-  __builtin_amdgcn_global_load_lds(
-      (const __attribute__((address_space(1))) void*)src,
-      (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-}
-
 // sigma = [0,2,3,1]: stored slot s holds logical chunk s ^ sigma(rb)
 DEV int sigma4(int x) { return (0x1320 >> (x * 4)) & 0xF; }
 
 // ---- staging state ----------------------------------------------------
-// Register-lean by construction (the BN=256 variant has ~96 VGPRs left
-// after the 128-reg accumulator + 32-reg fragment set): the thread's GA
+// Register-lean by construction (the 128-VGPR budget of 4 waves/SIMD
+// has to hold the accumulators and fragments too): the thread's GA
 // A-slots and GB B-slots all carry the SAME k-chunk (cg depends only on
 // the lane), so ONE (r,s,c) cursor per thread serves every slot;
 // per-slot state is a 32-bit element offset plus a packed s16x2 (u,v)
@@ -188,20 +168,18 @@ DEV const bf16* b_slot_addr(const ConvParams& p, const Cursor& cu,
 // k0, waves 4-7 fill k1) and B's cursor advances by 64.
 // LIN: 1x1 stride-1 pad-0 conv — the implicit-GEMM A operand is the
 // plain row-major tensor (no im2col arithmetic, no bounds tests)
-template <int MODE, int BM_, int BN_, int WR, int WC, bool PH2 = false,
-          bool LIN = false>
+template <int MODE, int BM_, int BN_, int WR, int WC, bool LIN>
 __global__ __launch_bounds__(THREADS2, 2)
 void conv_igemm2_kernel(ConvParams p) {
   constexpr int WM = BM_ / WR;       // wave tile M
   constexpr int WN = BN_ / WC;       // wave tile N
   constexpr int MF = WM / 16;        // acc M fragments
   constexpr int NF = WN / 16;        // acc N fragments
-  constexpr int MH = MF / 2;         // M fragments per phase
   constexpr int GA = BM_ * 32 / 8 / THREADS2;  // A glds per wave/slot
   constexpr bool COMB_B = (BN_ * 32 / 8) < THREADS2;
   constexpr int GB = COMB_B ? 1 : BN_ * 32 / 8 / THREADS2;
   static_assert(WR * WC == 8, "8 waves");
-  static_assert(GA >= 1 && MH >= 1, "tile vs thread count");
+  static_assert(GA >= 1 && MF >= 1, "tile vs thread count");
   static_assert(!COMB_B || BN_ == 64, "combined-B staging needs BN=64");
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -221,14 +199,7 @@ void conv_igemm2_kernel(ConvParams p) {
   const int fk = lane >> 4;
 
   const int nbn = (int)((p.Nd + BN_ - 1) / BN_);
-  int block = blockIdx.x;
-  {  // bijective XCD-aware remap: contiguous chunk per XCD
-    const int nwg = gridDim.x;
-    const int q = nwg / 8, rmd = nwg % 8;
-    const int xcd = block % 8, idx = block / 8;
-    block = (xcd < rmd ? xcd * (q + 1) : rmd * (q + 1) + (xcd - rmd) * q)
-            + idx;
-  }
+  const int block = xcd_remap(blockIdx.x, gridDim.x);
   const long bm = (long)(block / nbn) * BM_;
   const long bn = (long)(block % nbn) * BN_;
 
@@ -312,8 +283,6 @@ void conv_igemm2_kernel(ConvParams p) {
     for (int j = 0; j < NF; ++j)
       acc[i][j] = {0.f, 0.f, 0.f, 0.f};
 
-  bf16x8 bfr[NF];  // B fragments, retained across the two m-half phases
-
   // ---- prologue: stage K-tile 0 fully ----------------------------------
   stage_a(0, 0);
   stage_b(0, 0);  // combined form also covers k1 here
@@ -323,82 +292,53 @@ void conv_igemm2_kernel(ConvParams p) {
   wait_vmcnt<COMB_B ? GA : GA + GB>();
   __builtin_amdgcn_s_barrier();
 
-  // ---- main loop: 4 phases per K-tile ----------------------------------
-  // PH(msub, kh): ds_read fragments, issue one half-slot prefetch,
-  // barrier, MFMA cluster, (counted vmcnt), barrier.
-#define PH(M0, MC, KH, STAGE, VMW)                                       \
+  // ---- main loop: 2 phases per K-tile ----------------------------------
+  // PH(kh, stage, wait): ds_read the k-half's A and B fragments, issue
+  // the prefetch, barrier, MFMA cluster, counted vmcnt, barrier.
+#define PH(KH, STAGE, VMW)                                                \
   do {                                                                    \
-    bf16* la = aslot(cbuf, KH);                                           \
-    bf16x8 af[MC];                                                        \
+    const bf16* la = aslot(cbuf, KH);                                     \
+    const bf16* lb = bslot(cbuf, KH);                                     \
+    bf16x8 af[MF], bfr[NF];                                               \
     _Pragma("unroll")                                                     \
-    for (int mf = 0; mf < (MC); ++mf)                                     \
+    for (int mf = 0; mf < MF; ++mf)                                       \
       af[mf] = *reinterpret_cast<const bf16x8*>(                          \
-          la + (awoff + (M0) * (WM / 2) + mf * 16 + fr) * 32 + fchunk);   \
-    if ((M0) == 0) {                                                      \
-      bf16* lb = bslot(cbuf, KH);                                         \
-      _Pragma("unroll")                                                   \
-      for (int nf = 0; nf < NF; ++nf)                                     \
-        bfr[nf] = *reinterpret_cast<const bf16x8*>(                       \
-            lb + (bwoff + nf * 16 + fr) * 32 + fchunk);                   \
-    }                                                                     \
+          la + (awoff + mf * 16 + fr) * 32 + fchunk);                     \
+    _Pragma("unroll")                                                     \
+    for (int nf = 0; nf < NF; ++nf)                                       \
+      bfr[nf] = *reinterpret_cast<const bf16x8*>(                         \
+          lb + (bwoff + nf * 16 + fr) * 32 + fchunk);                     \
     STAGE;                                                                \
     __builtin_amdgcn_s_barrier();                                         \
     __builtin_amdgcn_s_setprio(1);                                        \
     _Pragma("unroll")                                                     \
-    for (int mf = 0; mf < (MC); ++mf)                                     \
+    for (int mf = 0; mf < MF; ++mf)                                       \
       _Pragma("unroll")                                                   \
       for (int nf = 0; nf < NF; ++nf)                                     \
-        acc[(M0) * MH + mf][nf] =                                         \
-            __builtin_amdgcn_mfma_f32_16x16x32_bf16(                      \
-                af[mf], bfr[nf], acc[(M0) * MH + mf][nf], 0, 0, 0);       \
+        acc[mf][nf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(            \
+            af[mf], bfr[nf], acc[mf][nf], 0, 0, 0);                       \
     __builtin_amdgcn_s_setprio(0);                                        \
     VMW;                                                                  \
     __builtin_amdgcn_s_barrier();                                         \
   } while (0)
 
-  // counted waits: end-of-ph1 guards this tile's k1 reads (allows the
-  // two units issued at ph0/ph1 to stay in flight); end-of-ph3 guards
-  // the next tile's k0 reads (allows ph2/ph3's units)
-  constexpr int V1 = COMB_B ? GA + 1 : GA + GB;
-  constexpr int V3 = COMB_B ? GA : GA + GB;
   for (int t = 0; t < nsteps; ++t) {
     const int cbuf = t & 1;
     const int nxt = cbuf ^ 1;
-    const bool more = (t + 1 < nsteps);
-    if (PH2) {
-      // 2 phases per K-tile (full-M x k-half, 2x the MFMA per barrier
-      // pair): both operand halves stage inside one phase, one counted
-      // vmcnt per phase, 1-phase prefetch slack. COMB_B stages B (both
-      // halves) once, in ph0.
-      if (more && COMB_B) {
-        PH(0, MF, 0, (stage_a(nxt, 0), stage_b(nxt, 0)),
-           wait_vmcnt<GA + 1>());
-        PH(0, MF, 1, stage_a(nxt, 1), wait_vmcnt<GA>());
-      } else if (more) {
-        PH(0, MF, 0, (stage_a(nxt, 0), stage_b(nxt, 0)),
-           wait_vmcnt<V1>());
-        PH(0, MF, 1, (stage_a(nxt, 1), stage_b(nxt, 1)),
-           wait_vmcnt<V1>());
-      } else {
-        PH(0, MF, 0, , wait_vmcnt<0>());
-        PH(0, MF, 1, , );
-      }
-    } else if (more) {
-      PH(0, MH, 0, stage_a(nxt, 0), );
-      PH(1, MH, 0, stage_b(nxt, 0), wait_vmcnt<V1>());
-      PH(0, MH, 1, stage_a(nxt, 1), );
-      if (COMB_B) {
-        PH(1, MH, 1, , wait_vmcnt<V3>());
-      } else {
-        PH(1, MH, 1, stage_b(nxt, 1), wait_vmcnt<V3>());
-      }
+    if (t + 1 < nsteps) {
+      // each wait leaves only its own phase's prefetch in flight, so
+      // the half the next phase reads has landed. COMB_B stages B (both
+      // halves, GB == 1) once, in the first phase.
+      PH(0, (stage_a(nxt, 0), stage_b(nxt, 0)), wait_vmcnt<GA + GB>());
+      if (COMB_B)
+        PH(1, stage_a(nxt, 1), wait_vmcnt<GA>());
+      else
+        PH(1, (stage_a(nxt, 1), stage_b(nxt, 1)), wait_vmcnt<GA + GB>());
     } else {
-      // last K-tile: nothing left to stage; the k1 halves may still be
-      // in flight, so the mid-tile wait drains fully
-      PH(0, MH, 0, , );
-      PH(1, MH, 0, , wait_vmcnt<0>());
-      PH(0, MH, 1, , );
-      PH(1, MH, 1, , );
+      // last K-tile: nothing left to stage; its k1 half may still be in
+      // flight, so the mid-tile wait drains fully
+      PH(0, , wait_vmcnt<0>());
+      PH(1, , );
     }
   }
 #undef PH
@@ -435,16 +375,8 @@ void conv_igemm2_kernel(ConvParams p) {
       const int ck = idx - r * CPR;
       const long row = bm + r;
       if (row >= p.M) continue;
-      long out_row = row;
-      if (MODE == 2) {
-        // class row -> scattered dx pixel (n, 2*ii+a, 2*jj+b)
-        const int hw = p.nh * p.nw;
-        const int n = (int)(row / hw);
-        const int rem = (int)(row - (long)n * hw);
-        const int ii = rem / p.nw, jj = rem - (rem / p.nw) * p.nw;
-        out_row = ((long)n * p.H + 2 * ii + p.cls_a) * p.W
-                  + 2 * jj + p.cls_b;
-      }
+      // class row -> scattered dx pixel
+      const long out_row = (MODE == 2) ? conv_class_dx_row(p, row) : row;
       const long colbase = bn + ck * 8;
       const bf16* src = img + r * BN_ + ck * 8;
       if (colbase + 8 <= p.Nd) {
@@ -458,59 +390,39 @@ void conv_igemm2_kernel(ConvParams p) {
   }
 }
 
+template <int MODE, int BM_, int BN_, int WR, int WC, bool LIN>
+void launch_tile(const ConvParams& p, hipStream_t stream) {
+  const long nbm = (p.M + BM_ - 1) / BM_;
+  const long nbn = (p.Nd + BN_ - 1) / BN_;
+  const size_t lds_bytes = 4 * (BM_ + BN_) * 32 * sizeof(bf16);
+  hipLaunchKernelGGL((conv_igemm2_kernel<MODE, BM_, BN_, WR, WC, LIN>),
+                     dim3((unsigned)(nbm * nbn)), dim3(THREADS2), lds_bytes,
+                     stream, p);
+}
+
+// High-occupancy tiles (116-122 VGPR -> 4 waves/SIMD, <= 80 KiB LDS ->
+// 2 blocks/CU): cross-block TLP hides the staging latency a 1-block/CU
+// 256-row tile pays in parked waves. Nd >= 96 tiles 128x128 with column
+// blocks; Nd in [48, 96) gets the 256x64 combined-B tile.
+template <int MODE, bool LIN>
+bool dispatch_tile(const ConvParams& p, hipStream_t stream) {
+  if (p.Nd >= 96)
+    launch_tile<MODE, 128, 128, 2, 4, LIN>(p, stream);
+  else if (p.Nd >= 48)
+    launch_tile<MODE, 256, 64, 4, 2, LIN>(p, stream);
+  else
+    return false;
+  return true;
+}
+
 template <int MODE>
 bool dispatch_v2(const ConvParams& p, hipStream_t stream) {
-  // DDLB_CONV_PH2=0 selects the 4-phase schedule for A/B (default: the
-  // 2-phase full-M schedule — half the barriers per K-tile; the PMC
-  // profile showed 37% of wave cycles parked on barriers at 4-phase)
-  const char* phe = getenv("DDLB_CONV_PH2");
-  const bool ph2 = !(phe && phe[0] == '0');
-  const bool lin = (MODE != 2 && p.R == 1 && p.S == 1 && p.stride == 1 &&
-                    p.pad == 0);
-#define LAUNCH2(BM_, BN_, WR, WC, PH2_)                                     \
-  do {                                                                      \
-    const long nbm = (p.M + (BM_) - 1) / (BM_);                             \
-    const long nbn = (p.Nd + (BN_) - 1) / (BN_);                            \
-    const size_t lds_bytes = 4 * ((BM_) + (BN_)) * 32 * sizeof(bf16);       \
-    if (lin)                                                                \
-      hipLaunchKernelGGL(                                                   \
-          (conv_igemm2_kernel<MODE, BM_, BN_, WR, WC, PH2_, true>),         \
-          dim3((unsigned)(nbm * nbn)), dim3(THREADS2),                      \
-          lds_bytes, stream, p);                                            \
-    else                                                                    \
-      hipLaunchKernelGGL(                                                   \
-          (conv_igemm2_kernel<MODE, BM_, BN_, WR, WC, PH2_, false>),        \
-          dim3((unsigned)(nbm * nbn)), dim3(THREADS2),                      \
-          lds_bytes, stream, p);                                            \
-  } while (0)
-  // BN=256 (acc 128 regs/wave) cannot fit beside the im2col staging
-  // state in the 256-VGPR/2-wave budget (measured 105-reg spill); the
-  // 256x128 tile (acc 64, ~204 VGPRs clean) serves all Nd >= 96 with
-  // column blocks. Nd in [48,96) gets a 512x64 tile (combined-B).
-  // Default: the high-occupancy 128x128 tile (116-122 VGPR -> 4
-  // waves/SIMD, 64 KiB LDS -> 2 blocks/CU): cross-block TLP hides the
-  // staging latency the 1-block 256x128 tile paid in parked waves
-  // (measured fwd 1.64->1.39 ms aggregate, dgrad 1.86->1.60 = 0.84x
-  // MIOpen). DDLB_CONV_TILE=b restores the big tile for A/B.
-  const char* te = getenv("DDLB_CONV_TILE");
-  const bool big_tile = te && te[0] == 'b';
-  if (p.Nd >= 96 && !big_tile) {
-    if (ph2) LAUNCH2(128, 128, 2, 4, true);
-    else LAUNCH2(128, 128, 2, 4, false);
-  } else if (p.Nd >= 96) {
-    if (ph2) LAUNCH2(256, 128, 2, 4, true);
-    else LAUNCH2(256, 128, 2, 4, false);
-  } else if (p.Nd >= 48 && !big_tile) {
-    if (ph2) LAUNCH2(256, 64, 4, 2, true);
-    else LAUNCH2(256, 64, 4, 2, false);
-  } else if (p.Nd >= 48) {
-    if (ph2) LAUNCH2(512, 64, 8, 1, true);
-    else LAUNCH2(512, 64, 8, 1, false);
-  } else {
-    return false;
+  // the parity-class gather (MODE 2) is never a plain row-major operand
+  if constexpr (MODE != 2) {
+    if (p.R == 1 && p.S == 1 && p.stride == 1 && p.pad == 0)
+      return dispatch_tile<MODE, true>(p, stream);
   }
-#undef LAUNCH2
-  return true;
+  return dispatch_tile<MODE, false>(p, stream);
 }
 
 }  // namespace

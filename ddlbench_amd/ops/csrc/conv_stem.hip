@@ -34,15 +34,13 @@
 // Limits (checked in bindings.hip): C in 1..4, square R in {3,5,7},
 // stride in {1,2}, 0 <= pad <= R/2, K % 8 == 0, K <= 128.
 
-#include "common.h"
+#include "mfma_common.h"
+#include "launchers.h"
 #include <stdint.h>
 #include <stdexcept>
 #include <string>
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) short bf16x8s;
-typedef __attribute__((ext_vector_type(4))) float f32x4s;
 
 constexpr int ST_THREADS = 256;
 constexpr int ST_TH = 8;          // output rows per tile
@@ -177,7 +175,7 @@ void conv_stem_fwd_kernel(StemParams q) {
     for (int j = 0; j < 8; ++j)
       aoff[ks][j] = kd_offset(q, ks * 32 + 8 * (lane >> 4) + j);
   // elements of the last k-step past Kd are masked to zero
-  bf16x8s tailmask;
+  bf16x8 tailmask;
 #pragma unroll
   for (int j = 0; j < 8; ++j)
     tailmask[j] =
@@ -193,7 +191,7 @@ void conv_stem_fwd_kernel(StemParams q) {
     const int sh = load_patch(q, t, patch, tid);
     __syncthreads();
 
-    f32x4s acc[2][4];
+    f32x4 acc[2][4];
 #pragma unroll
     for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -204,7 +202,7 @@ void conv_stem_fwd_kernel(StemParams q) {
 #pragma unroll
     for (int ks = 0; ks < ST_MAXKS; ++ks) {
       if (ks < q.nks) {
-        bf16x8s x0, x1;
+        bf16x8 x0, x1;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           x0[j] = (short)pa[aoff[ks][j]];
@@ -217,7 +215,7 @@ void conv_stem_fwd_kernel(StemParams q) {
 #pragma unroll
         for (int nb = 0; nb < 4; ++nb) {
           if (nb < nnb) {
-            const bf16x8s wf = *reinterpret_cast<const bf16x8s*>(
+            const bf16x8 wf = *reinterpret_cast<const bf16x8*>(
                 &wl[(nb * 16 + (lane & 15)) * wp + ks * 32 +
                     (lane >> 4) * 8]);
             acc[0][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
@@ -297,7 +295,7 @@ void conv_stem_wgrad_kernel(StemParams q) {
   // (row 2*ks + (lane>>5), col 8*((lane>>4)&1) + j)
   const int pix0 = (lane >> 5) * q.stride * q.pitch + 8 * ((lane >> 4) & 1) * sC;
 
-  f32x4s acc[4][4];   // [k block][col block i]
+  f32x4 acc[4][4];   // [k block][col block i]
 #pragma unroll
   for (int a = 0; a < 4; ++a)
 #pragma unroll
@@ -332,7 +330,7 @@ void conv_stem_wgrad_kernel(StemParams q) {
     for (int ks = 0; ks < ST_TP / 32; ++ks) {
       const unsigned short* pp =
           patch + sh + pix0 + (2 * ks) * q.stride * q.pitch;
-      bf16x8s bf[4];
+      bf16x8 bf[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         if (wid + 4 * i < ncb) {
@@ -343,7 +341,7 @@ void conv_stem_wgrad_kernel(StemParams q) {
 #pragma unroll
       for (int a = 0; a < 4; ++a) {
         if (a < nnb) {
-          const bf16x8s af = *reinterpret_cast<const bf16x8s*>(
+          const bf16x8 af = *reinterpret_cast<const bf16x8*>(
               &dyt[(a * 16 + (lane & 15)) * ST_DPITCH + ks * 32 +
                    (lane >> 4) * 8]);
 #pragma unroll
@@ -419,16 +417,17 @@ void fill_geometry(StemParams& q, long max_blocks) {
 }  // namespace
 
 // blocks per K tile the wgrad launch will use (= partial slabs)
-int conv_stem_wgrad_chunks(int N, int OH, int OW, int K) {
+int ddlb::conv_stem_wgrad_chunks(int N, int OH, int OW, int K) {
   const long nsp = (long)N * ((OH + ST_TH - 1) / ST_TH) *
                    ((OW + ST_TW - 1) / ST_TW);
   const int nkt = (K + ST_KT - 1) / ST_KT;
   return (int)i64max(i64min(nsp, 512 / nkt), 1);
 }
 
-void launch_conv_stem_fwd(const void* x, const void* w, void* y, int N,
-                          int H, int W, int C, int K, int OH, int OW, int R,
-                          int stride, int pad, hipStream_t stream) {
+void ddlb::launch_conv_stem_fwd(const void* x, const void* w, void* y, int N,
+                                int H, int W, int C, int K, int OH, int OW,
+                                int R, int stride, int pad,
+                                hipStream_t stream) {
   StemParams q = {};
   q.x = (const unsigned short*)x;
   q.w = (const unsigned short*)w;
@@ -441,10 +440,10 @@ void launch_conv_stem_fwd(const void* x, const void* w, void* y, int N,
   HIP_CHECK_LAST();
 }
 
-void launch_conv_stem_wgrad(const void* x, const void* dy, float* dw,
-                            float* part, int N, int H, int W, int C, int K,
-                            int OH, int OW, int R, int stride, int pad,
-                            hipStream_t stream) {
+void ddlb::launch_conv_stem_wgrad(const void* x, const void* dy, float* dw,
+                                  float* part, int N, int H, int W, int C,
+                                  int K, int OH, int OW, int R, int stride,
+                                  int pad, hipStream_t stream) {
   StemParams q = {};
   q.x = (const unsigned short*)x;
   q.dy = (const unsigned short*)dy;

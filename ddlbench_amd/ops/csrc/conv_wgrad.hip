@@ -7,43 +7,37 @@
 // pixels p. Both operands are p-major in memory (transposed from the
 // MFMA fragment layout), so tiles stage into a ds_read_b64_tr_b16 image
 // and fragments come out of the HARDWARE TRANSPOSE READ — one b64-class
-// LDS instruction per 4 fragment elements instead of the per-element
-// scalar gathers of the round-1 kernel (its 2.3x-vs-MIOpen gap).
+// LDS instruction per 4 fragment elements instead of per-element
+// scalar gathers.
 //
-// Structure (v2, default):
-//   * 64k x 64rsc tile, BP=64 pixels per step, 256 threads (4 waves,
-//     one 16-rsc column group each).
+// Structure:
+//   * TKt x TRt dw tile (64 or 128 per side, by shape), BP=64 pixels
+//     per step, 256 or 512 threads.
 //   * tr image per operand: 4 column groups x [two p-parity
 //     sub-images] x [p/8][4][16] halfword blocks; glds stages it with
 //     lane-linear 16-B chunks whose SOURCE index is decoded per slot
 //     (cdna_hip_programming.md T10: lane l of a 16-lane group reads
 //     column l&15 of a [4][16] block at lane-linear 8-B addresses).
-//   * 3-buffer LDS ring (48 KiB), staging 2 steps ahead, counted
-//     s_waitcnt vmcnt(4) per step, raw s_barrier (never __syncthreads
-//     with glds in flight).
+//   * 3-buffer LDS ring, staging 2 steps ahead, counted s_waitcnt
+//     vmcnt(GA+GB) per step, raw s_barrier (never __syncthreads with
+//     glds in flight). The 128x128 tile runs a 2-buffer ring instead
+//     and overlaps through its co-resident second block.
 //   * split-P partial slabs [split][K][RSC] fp32 + a combine kernel —
-//     no global atomics (a C64K64R1 layer would serialize ~2048 f64
-//     atomic adds per dw element).
-// DDLB_WGRAD_V2=0 falls back to the round-1 scalar-gather kernel.
+//     no per-tile global atomics (a C64K64R1 layer would serialize
+//     ~2048 atomic adds per dw element).
 //
 // Constraints: bf16, K % 8 == 0, C % 8 == 0.
 
-#include "common.h"
+#include "mfma_common.h"
+#include "launchers.h"
 #include <stdint.h>
 #include <stdexcept>
-#include <stdlib.h>
 #include <string>
 
 using bf16 = __hip_bfloat16;
-typedef __attribute__((ext_vector_type(8))) short bf16x8w;
-typedef __attribute__((ext_vector_type(4))) short bf16x4w;
-typedef __attribute__((ext_vector_type(4))) float f32x4w;
 typedef __attribute__((address_space(3))) const short* lds_cptr;
 
 #define WG_BKP 64     // p rows per step
-#define WG_TK 64      // k tile
-#define WG_TR 64      // rsc tile
-#define WG_THREADS 256
 
 struct WgradParams {
   const bf16* x;      // (N,H,W,C) memory
@@ -57,137 +51,7 @@ struct WgradParams {
   int split_p;        // p-chunks per (k,rsc) tile
 };
 
-// ---------------------------------------------------------------------
-// v1 kernel (round 1): scalar transposed gathers. Kept for A/B and as
-// the DDLB_WGRAD_V2=0 fallback.
-__global__ __launch_bounds__(WG_THREADS, 2)
-void conv_wgrad_kernel(WgradParams q) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  bf16* la = reinterpret_cast<bf16*>(smem);                 // [64p][64k]
-  bf16* lb = la + WG_BKP * WG_TK;                           // [64p][64rsc]
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
-
-  const int nk = (q.K + WG_TK - 1) / WG_TK;
-  const int nr = (int)((q.RSC + WG_TR - 1) / WG_TR);
-  const long block = blockIdx.x;
-  const long kb = (block % nk) * WG_TK;
-  const long rb = ((block / nk) % nr) * WG_TR;
-  const int ps_idx = (int)(block / ((long)nk * nr));
-  const long p_per = (q.P + q.split_p - 1) / q.split_p;
-  const long p_begin = ps_idx * p_per;
-  const long p_end = i64min(p_begin + p_per, q.P);
-
-  const int nsteps = (int)((p_end - p_begin + WG_BKP - 1) / WG_BKP);
-
-  const int wn = wid * 16;
-  f32x4w acc[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) acc[i] = {0.f, 0.f, 0.f, 0.f};
-
-  for (int t = 0; t < nsteps; ++t) {
-    const long p0 = p_begin + (long)t * WG_BKP;
-#pragma unroll
-    for (int l = 0; l < 2; ++l) {
-      const int ca = l * WG_THREADS + tid;
-      const int prow = ca >> 3;
-      const int cg = (ca & 7) ^ (prow & 7);
-      const long p = p0 + prow;
-      const bf16* src = q.zero;
-      if (p < p_end && kb + cg * 8 < q.K)
-        src = q.dy + p * q.K + kb + cg * 8;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)src,
-          (__attribute__((address_space(3))) void*)(la + ca * 8), 16, 0,
-          0);
-    }
-#pragma unroll
-    for (int l = 0; l < 2; ++l) {
-      const int ca = l * WG_THREADS + tid;
-      const int prow = ca >> 3;
-      const int cg = (ca & 7) ^ (prow & 7);
-      const long p = p0 + prow;
-      const long rsc = rb + cg * 8;
-      const bf16* src = q.zero;
-      if (p < p_end && rsc < q.RSC) {
-        const int ohw = q.OH * q.OW;
-        const int n = (int)(p / ohw);
-        const int rem = (int)(p - (long)n * ohw);
-        const int oh = rem / q.OW, ow = rem - (rem / q.OW) * q.OW;
-        const int c0 = (int)(rsc % q.C);
-        const int rs = (int)(rsc / q.C);
-        const int r = rs / q.S, s = rs - (rs / q.S) * q.S;
-        const int ih = oh * q.stride + r - q.pad;
-        const int iw = ow * q.stride + s - q.pad;
-        if (ih >= 0 && ih < q.H && iw >= 0 && iw < q.W)
-          src = q.x + (((long)n * q.H + ih) * q.W + iw) * q.C + c0;
-      }
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)src,
-          (__attribute__((address_space(3))) void*)(lb + ca * 8), 16, 0,
-          0);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-
-    // element (p, col) lives at p*64 + ((col>>3)^(p&7))*8 + (col&7)
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8w bfrag;
-      {
-        const int col = wn + (lane & 15);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const int p = ks * 32 + (lane >> 4) * 8 + e;
-          bfrag[e] = reinterpret_cast<const short*>(lb)[
-              p * WG_TR + ((col >> 3) ^ (p & 7)) * 8 + (col & 7)];
-        }
-      }
-#pragma unroll
-      for (int mf = 0; mf < 4; ++mf) {
-        bf16x8w afrag;
-        const int col = mf * 16 + (lane & 15);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const int p = ks * 32 + (lane >> 4) * 8 + e;
-          afrag[e] = reinterpret_cast<const short*>(la)[
-              p * WG_TK + ((col >> 3) ^ (p & 7)) * 8 + (col & 7)];
-        }
-        acc[mf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            afrag, bfrag, acc[mf], 0, 0, 0);
-      }
-    }
-    __syncthreads();
-  }
-
-  // fp32 atomic accumulation into dw (v1 path keeps atomics)
-#pragma unroll
-  for (int mf = 0; mf < 4; ++mf) {
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-      const long k = kb + mf * 16 + (lane >> 4) * 4 + reg;
-      const long rsc = rb + wn + (lane & 15);
-      if (k < q.K && rsc < q.RSC)
-        atomicAdd(&q.dw[k * q.RSC + rsc], acc[mf][reg]);
-    }
-  }
-}
-
-// ---------------------------------------------------------------------
-// v2: hardware-transpose-read pipeline.
 namespace {
-
-template <int N> DEV void wait_step_vmcnt() {
-  static_assert(N >= 0 && N <= 8, "vmcnt");
-  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-  else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-  else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-}
 
 // tr image geometry (per operand, per buffer): 4 column groups g of 16,
 // each a pair of p-parity sub-images of [BP/8][4][16] halfword blocks:
@@ -203,17 +67,17 @@ DEV void wg_decode_chunk(int d, int& p, int& ch) {
   ch = g * 16 + (r2 & 1) * 8;
 }
 
-DEV bf16x8w wg_tr_frag(const short* img, int group, int ks, int lane) {
+DEV bf16x8 wg_tr_frag(const short* img, int group, int ks, int lane) {
   // fragment (m/n-col = lane&15, p = ks*32 + (lane>>4)*8 + e):
   // two tr reads (p parity halves) at lane-linear 8-B addresses
-  bf16x4w lo, hi;
+  bf16x4 lo, hi;
   lds_cptr base = (lds_cptr)(img + group * (WG_BKP * 16) + ks * 4 * 64 +
                              lane * 4);
   asm volatile("ds_read_b64_tr_b16 %0, %2\n\t"
                "ds_read_b64_tr_b16 %1, %2 offset:%3"
                : "=&v"(lo), "=&v"(hi)
                : "v"(base), "i"(WG_BKP * 8 * 2));
-  bf16x8w f;
+  bf16x8 f;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     f[e] = lo[e];
@@ -227,8 +91,7 @@ DEV bf16x8w wg_tr_frag(const short* img, int group, int ks, int lane) {
 // A re-reads x nr, B x nk).
 // R1: 1x1 stride-1 pad-0 conv — B (im2col x) degenerates to the plain
 // row-major tensor; skip the per-step carry chain and bounds tests
-template <int TKt, int TRt, int WR, int WC, int TPB, bool R1 = false,
-          bool RING2 = false>
+template <int TKt, int TRt, int WR, int WC, int TPB, bool R1, bool RING2>
 __global__ __launch_bounds__(TPB, RING2 ? 4 : 2)
 void conv_wgrad2_kernel(WgradParams q) {
   constexpr int NBUF = RING2 ? 2 : 3;
@@ -315,9 +178,7 @@ void conv_wgrad2_kernel(WgradParams q) {
           (a_chok[j] && a_pabs[j] + (long)t * WG_BKP < plim)
               ? a_src[j] + (long)t * WG_BKP * q.K
               : q.zero;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)src,
-          (__attribute__((address_space(3))) void*)(la + d * 8), 16, 0, 0);
+      glds16(src, la + d * 8);
     }
 #pragma unroll
     for (int j = 0; j < GB; ++j) {
@@ -337,9 +198,7 @@ void conv_wgrad2_kernel(WgradParams q) {
           src = q.x + (((long)b_n[j] * q.H + ih) * q.W + iw) * q.C +
                 b_c0[j];
       }
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)src,
-          (__attribute__((address_space(3))) void*)(lb + d * 8), 16, 0, 0);
+      glds16(src, lb + d * 8);
       if (!R1) {
         // advance the pixel coords by BP rows (carry chain)
         int oh = b_ohw[j] >> 16, ow = (b_ohw[j] & 0xffff) + WG_BKP;
@@ -357,7 +216,7 @@ void conv_wgrad2_kernel(WgradParams q) {
 
   const int wk = wid / WC;
   const int wc = wid % WC;
-  f32x4w acc[MFS][NFS];
+  f32x4 acc[MFS][NFS];
 #pragma unroll
   for (int i = 0; i < MFS; ++i)
 #pragma unroll
@@ -367,9 +226,9 @@ void conv_wgrad2_kernel(WgradParams q) {
   stage(0, 0);
   if (!RING2 && nsteps > 1) {
     stage(1, 1);
-    wait_step_vmcnt<GA + GB>();  // step 0 landed, step 1 in flight
+    wait_vmcnt<GA + GB>();  // step 0 landed, step 1 in flight
   } else {
-    wait_step_vmcnt<0>();
+    wait_vmcnt<0>();
   }
   __builtin_amdgcn_s_barrier();
 
@@ -380,7 +239,7 @@ void conv_wgrad2_kernel(WgradParams q) {
     // halves (ks) back to back
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      bf16x8w af[MFS], bf_[NFS];
+      bf16x8 af[MFS], bf_[NFS];
 #pragma unroll
       for (int nf = 0; nf < NFS; ++nf)
         bf_[nf] = wg_tr_frag(lb, wc * NFS + nf, ks, lane);
@@ -403,12 +262,12 @@ void conv_wgrad2_kernel(WgradParams q) {
       // Overlap comes from the co-resident second block, not from
       // loads spanning barriers.
       if (t + 1 < nsteps) stage((t + 1) % 2, t + 1);
-      wait_step_vmcnt<0>();
+      wait_vmcnt<0>();
     } else if (t + 2 < nsteps) {
       stage((t + 2) % 3, t + 2);
-      wait_step_vmcnt<GA + GB>();
+      wait_vmcnt<GA + GB>();
     } else {
-      wait_step_vmcnt<0>();
+      wait_vmcnt<0>();
     }
     __builtin_amdgcn_s_barrier();
   }
@@ -451,13 +310,27 @@ __global__ void wgrad_combine_kernel(const float* __restrict__ part,
   }
 }
 
+// R1 is a property of the conv, the tile a property of the dw shape
+template <int TKt, int TRt, int WR, int WC, int TPB, bool RING2>
+void wg_launch(const WgradParams& q, bool r1, unsigned grid, size_t lds,
+               hipStream_t stream) {
+  if (r1)
+    hipLaunchKernelGGL(
+        (conv_wgrad2_kernel<TKt, TRt, WR, WC, TPB, true, RING2>),
+        dim3(grid), dim3(TPB), lds, stream, q);
+  else
+    hipLaunchKernelGGL(
+        (conv_wgrad2_kernel<TKt, TRt, WR, WC, TPB, false, RING2>),
+        dim3(grid), dim3(TPB), lds, stream, q);
+}
+
 }  // namespace
 
-void launch_conv_wgrad(const void* x, const void* dy, float* dw,
-                       float* part_ws, long part_cap, const void* zero,
-                       int N, int H, int W, int C, int K,
-                       int OH, int OW, int R, int S, int stride, int pad,
-                       hipStream_t stream) {
+void ddlb::launch_conv_wgrad(const void* x, const void* dy, float* dw,
+                             float* part_ws, long part_cap, const void* zero,
+                             int N, int H, int W, int C, int K, int OH, int OW,
+                             int R, int S, int stride, int pad,
+                             hipStream_t stream) {
   WgradParams q;
   q.x = (const bf16*)x;
   q.dy = (const bf16*)dy;
@@ -468,82 +341,42 @@ void launch_conv_wgrad(const void* x, const void* dy, float* dw,
   q.R = R; q.S = S; q.stride = stride; q.pad = pad;
   q.P = (long)N * OH * OW;
   q.RSC = (long)R * S * C;
-  const long nk = (K + WG_TK - 1) / WG_TK;
-  const long nr = (q.RSC + WG_TR - 1) / WG_TR;
 
-  const char* v2e = getenv("DDLB_WGRAD_V2");
-  const bool use_v2 = !(v2e && v2e[0] == '0') && part_ws != nullptr;
-
-  if (use_v2) {
-    // tile by shape: square 128 where possible (least re-staging),
-    // rectangular when only one dim allows it
-    const bool bigK = K >= 128, bigR = q.RSC >= 128;
-    const long TKt = bigK ? 128 : 64, TRt = bigR ? 128 : 64;
-    const long nk2 = (K + TKt - 1) / TKt;
-    const long nr2 = (q.RSC + TRt - 1) / TRt;
-    long split = 2048 / i64max(nk2 * nr2, 1);
-    split = i64max(i64min(split, (q.P + WG_BKP - 1) / WG_BKP), 1);
-    split = i64min(split, 256);  // combine traffic cap
-    if (split > 1)
-      split = i64min(split, part_cap / i64max(q.K * q.RSC, 1));
-    split = i64max(split, 1);
-    q.split_p = (int)split;
-    const bool bigsq = bigK && bigR;
-    const size_t lds2 =
-        (bigsq ? 2 : 3) * WG_BKP * (TKt + TRt) * sizeof(bf16);
-    // big tile: 512 threads (8 waves = 2/SIMD at the 96 KiB-LDS
-    // 1-block/CU occupancy); small tile: 256 threads x 3 blocks/CU
-    const bool r1 = (R == 1 && S == 1 && stride == 1 && pad == 0);
-    const unsigned grid2 = (unsigned)(nk2 * nr2 * q.split_p);
-#define WG_LAUNCH(TK_, TR_, WR_, WC_, TPB_)                                 \
-    do {                                                                    \
-      if (r1)                                                               \
-        hipLaunchKernelGGL(                                                 \
-            (conv_wgrad2_kernel<TK_, TR_, WR_, WC_, TPB_, true>),           \
-            dim3(grid2), dim3(TPB_), lds2, stream, q);                      \
-      else                                                                  \
-        hipLaunchKernelGGL(                                                 \
-            (conv_wgrad2_kernel<TK_, TR_, WR_, WC_, TPB_, false>),          \
-            dim3(grid2), dim3(TPB_), lds2, stream, q);                      \
-    } while (0)
-    if (bigsq) {
-      if (r1)
-        hipLaunchKernelGGL(
-            (conv_wgrad2_kernel<128, 128, 2, 4, 512, true, true>),
-            dim3(grid2), dim3(512), lds2, stream, q);
-      else
-        hipLaunchKernelGGL(
-            (conv_wgrad2_kernel<128, 128, 2, 4, 512, false, true>),
-            dim3(grid2), dim3(512), lds2, stream, q);
-    }
-    else if (!bigK && bigR) WG_LAUNCH(64, 128, 1, 4, 256);
-    else if (bigK && !bigR) WG_LAUNCH(128, 64, 4, 1, 256);
-    else WG_LAUNCH(64, 64, 1, 4, 256);
-#undef WG_LAUNCH
-    if (q.split_p > 1) {
-      const long total = q.K * q.RSC;
-      const int blocks = (int)i64min((total + 255) / 256, 2048);
-      const int psb = (q.split_p + 63) / 64;
-      // multi-chunk combine accumulates with atomics -> dw must be 0
-      // (dw arrives as torch::empty; the single-chunk combine writes)
-      if (psb > 1)
-        hipMemsetAsync(dw, 0, total * sizeof(float), stream);
-      hipLaunchKernelGGL(wgrad_combine_kernel, dim3(blocks, psb),
-                         dim3(256), 0,
-                         stream, part_ws, dw, total, total, q.split_p);
-    }
-    HIP_CHECK_LAST();
-    return;
-  }
-
+  // tile by shape: square 128 where possible (least re-staging),
+  // rectangular when only one dim allows it
+  const bool bigK = K >= 128, bigR = q.RSC >= 128;
+  const long TKt = bigK ? 128 : 64, TRt = bigR ? 128 : 64;
+  const long nk = (K + TKt - 1) / TKt;
+  const long nr = (q.RSC + TRt - 1) / TRt;
   long split = 2048 / i64max(nk * nr, 1);
   split = i64max(i64min(split, (q.P + WG_BKP - 1) / WG_BKP), 1);
+  split = i64min(split, 256);  // combine traffic cap
+  if (split > 1)
+    split = i64min(split, part_cap / i64max(q.K * q.RSC, 1));
+  split = i64max(split, 1);
   q.split_p = (int)split;
-  // v1 accumulates with atomics -> zero dw (arrives as torch::empty)
-  hipMemsetAsync(dw, 0, q.K * q.RSC * sizeof(float), stream);
-  const size_t lds_bytes = (WG_BKP * WG_TK + WG_BKP * WG_TR) * sizeof(bf16);
-  hipLaunchKernelGGL(conv_wgrad_kernel,
-                     dim3((unsigned)(nk * nr * q.split_p)),
-                     dim3(WG_THREADS), lds_bytes, stream, q);
+  const bool bigsq = bigK && bigR;
+  const size_t lds =
+      (bigsq ? 2 : 3) * WG_BKP * (TKt + TRt) * sizeof(bf16);
+  // square tile: 512 threads on a 2-buffer ring (64 KiB, 2 blocks/CU);
+  // smaller tiles: 256 threads on the 3-buffer ring
+  const bool r1 = (R == 1 && S == 1 && stride == 1 && pad == 0);
+  const unsigned grid = (unsigned)(nk * nr * q.split_p);
+  if (bigsq) wg_launch<128, 128, 2, 4, 512, true>(q, r1, grid, lds, stream);
+  else if (bigR) wg_launch<64, 128, 1, 4, 256, false>(q, r1, grid, lds, stream);
+  else if (bigK) wg_launch<128, 64, 4, 1, 256, false>(q, r1, grid, lds, stream);
+  else wg_launch<64, 64, 1, 4, 256, false>(q, r1, grid, lds, stream);
+  if (q.split_p > 1) {
+    const long total = q.K * q.RSC;
+    const int blocks = (int)i64min((total + 255) / 256, 2048);
+    const int psb = (q.split_p + 63) / 64;
+    // multi-chunk combine accumulates with atomics -> dw must be 0
+    // (dw arrives as torch::empty; the single-chunk combine writes)
+    if (psb > 1)
+      hipMemsetAsync(dw, 0, total * sizeof(float), stream);
+    hipLaunchKernelGGL(wgrad_combine_kernel, dim3(blocks, psb),
+                       dim3(256), 0,
+                       stream, part_ws, dw, total, total, q.split_p);
+  }
   HIP_CHECK_LAST();
 }

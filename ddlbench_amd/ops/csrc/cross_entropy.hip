@@ -9,6 +9,7 @@
 // materialized softmax tensor.
 
 #include "common.h"
+#include "launchers.h"
 #include <stdint.h>
 #include <stdexcept>
 #include <string>
@@ -121,9 +122,9 @@ __global__ void ce_bwd_kernel(const T* __restrict__ logits,
 }
 
 template <typename T>
-void launch_ce_fwd(const T* logits, const int64_t* target, float* lse,
-                   float* loss_sum, int64_t B, int64_t K,
-                   hipStream_t stream) {
+void ddlb::launch_ce_fwd(const T* logits, const int64_t* target, float* lse,
+                         float* loss_sum, int64_t B, int64_t K,
+                         hipStream_t stream) {
   if (K >= 4096) {
     const bool vec = (K % 8 == 0) && sizeof(T) == 2;
     if (vec)
@@ -143,9 +144,9 @@ void launch_ce_fwd(const T* logits, const int64_t* target, float* lse,
 }
 
 template <typename T>
-void launch_ce_bwd(const T* logits, const int64_t* target, const float* lse,
-                   const float* gscale, T* dx, int64_t B, int64_t K,
-                   hipStream_t stream) {
+void ddlb::launch_ce_bwd(const T* logits, const int64_t* target,
+                         const float* lse, const float* gscale, T* dx,
+                         int64_t B, int64_t K, hipStream_t stream) {
   const int block = 256;
   int64_t want = (B * K + block - 1) / block;
   const int grid = (int)i64min(want > 0 ? want : 1, 256 * 8);
@@ -155,11 +156,12 @@ void launch_ce_bwd(const T* logits, const int64_t* target, const float* lse,
 }
 
 #define INSTANTIATE(T)                                                     \
-  template void launch_ce_fwd<T>(const T*, const int64_t*, float*, float*, \
-                                 int64_t, int64_t, hipStream_t);           \
-  template void launch_ce_bwd<T>(const T*, const int64_t*, const float*,   \
-                                 const float*, T*, int64_t, int64_t,       \
-                                 hipStream_t);
+  template void ddlb::launch_ce_fwd<T>(                                    \
+      const T*, const int64_t*, float*, float*, int64_t, int64_t,          \
+      hipStream_t);                                                        \
+  template void ddlb::launch_ce_bwd<T>(                                    \
+      const T*, const int64_t*, const float*, const float*, T*, int64_t,   \
+      int64_t, hipStream_t);
 INSTANTIATE(float)
 INSTANTIATE(__hip_bfloat16)
 #undef INSTANTIATE

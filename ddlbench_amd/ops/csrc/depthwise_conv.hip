@@ -7,6 +7,7 @@
 // the read-only cache. NCHW.
 
 #include "common.h"
+#include "launchers.h"
 #include <stdint.h>
 #include <stdexcept>
 #include <string>
@@ -295,9 +296,10 @@ static inline int ew_grid(int64_t total, int block) {
 }
 
 template <typename T>
-void launch_dw3x3_fwd(const T* x, const float* w, T* y, int64_t N, int64_t C,
-                      int64_t H, int64_t W, int64_t OH, int64_t OW,
-                      int stride_, int nhwc, hipStream_t stream) {
+void ddlb::launch_dw3x3_fwd(const T* x, const float* w, T* y, int64_t N,
+                            int64_t C, int64_t H, int64_t W, int64_t OH,
+                            int64_t OW, int stride_, int nhwc,
+                            hipStream_t stream) {
   const int block = 256;
   if (nhwc && sizeof(T) == 2 && C % 8 == 0) {
     const int CG8 = (int)i64min(C / 8, 64);
@@ -326,10 +328,10 @@ void launch_dw3x3_fwd(const T* x, const float* w, T* y, int64_t N, int64_t C,
 }
 
 template <typename T>
-void launch_dw3x3_bwd_dx(const T* dy, const float* w, T* dx, int64_t N,
-                         int64_t C, int64_t H, int64_t W, int64_t OH,
-                         int64_t OW, int stride_, int nhwc,
-                         hipStream_t stream) {
+void ddlb::launch_dw3x3_bwd_dx(const T* dy, const float* w, T* dx, int64_t N,
+                               int64_t C, int64_t H, int64_t W, int64_t OH,
+                               int64_t OW, int stride_, int nhwc,
+                               hipStream_t stream) {
   const int block = 256;
   if (nhwc && sizeof(T) == 2 && C % 8 == 0) {
     const int CG8 = (int)i64min(C / 8, 64);
@@ -358,10 +360,10 @@ void launch_dw3x3_bwd_dx(const T* dy, const float* w, T* dx, int64_t N,
 }
 
 template <typename T>
-void launch_dw3x3_bwd_dw(const T* x, const T* dy, double* dw, int64_t N,
-                         int64_t C, int64_t H, int64_t W, int64_t OH,
-                         int64_t OW, int stride_, int nhwc,
-                         hipStream_t stream) {
+void ddlb::launch_dw3x3_bwd_dw(const T* x, const T* dy, double* dw, int64_t N,
+                               int64_t C, int64_t H, int64_t W, int64_t OH,
+                               int64_t OW, int stride_, int nhwc,
+                               hipStream_t stream) {
   const int block = 256;
   if (nhwc && sizeof(T) == 2 && C % 8 == 0) {
     const int CG8 = (int)i64min(C / 8, 64);
@@ -392,15 +394,15 @@ void launch_dw3x3_bwd_dw(const T* x, const T* dy, double* dw, int64_t N,
 }
 
 #define INSTANTIATE(T)                                                       \
-  template void launch_dw3x3_fwd<T>(const T*, const float*, T*, int64_t,     \
-                                    int64_t, int64_t, int64_t, int64_t,      \
-                                    int64_t, int, int, hipStream_t);         \
-  template void launch_dw3x3_bwd_dx<T>(const T*, const float*, T*, int64_t,  \
-                                       int64_t, int64_t, int64_t, int64_t,   \
-                                       int64_t, int, int, hipStream_t);      \
-  template void launch_dw3x3_bwd_dw<T>(const T*, const T*, double*, int64_t, \
-                                       int64_t, int64_t, int64_t, int64_t,   \
-                                       int64_t, int, int, hipStream_t);
+  template void ddlb::launch_dw3x3_fwd<T>(                                   \
+      const T*, const float*, T*, int64_t, int64_t, int64_t, int64_t,        \
+      int64_t, int64_t, int, int, hipStream_t);                              \
+  template void ddlb::launch_dw3x3_bwd_dx<T>(                                \
+      const T*, const float*, T*, int64_t, int64_t, int64_t, int64_t,        \
+      int64_t, int64_t, int, int, hipStream_t);                              \
+  template void ddlb::launch_dw3x3_bwd_dw<T>(                                \
+      const T*, const T*, double*, int64_t, int64_t, int64_t, int64_t,       \
+      int64_t, int64_t, int, int, hipStream_t);
 INSTANTIATE(float)
 INSTANTIATE(__hip_bfloat16)
 #undef INSTANTIATE

@@ -19,6 +19,7 @@
 // element against 12-20 bytes of traffic — noise for a memory-bound op.
 
 #include "common.h"
+#include "launchers.h"
 #include <stdint.h>
 #include <stdexcept>
 #include <string>
@@ -91,11 +92,12 @@ __global__ void fused_adam_kernel(
 }
 
 template <typename T>
-void launch_fused_adam(uintptr_t* params, uintptr_t* grads, uintptr_t* ms,
-                       uintptr_t* vs, const int64_t* prefix, int n_tensors,
-                       int64_t total, float lr, float beta1, float beta2,
-                       float eps, float wd, float bc1, float bc2,
-                       int decoupled_wd, hipStream_t stream) {
+void ddlb::launch_fused_adam(uintptr_t* params, uintptr_t* grads, uintptr_t* ms,
+                             uintptr_t* vs, const int64_t* prefix,
+                             int n_tensors, int64_t total, float lr,
+                             float beta1, float beta2, float eps, float wd,
+                             float bc1, float bc2, int decoupled_wd,
+                             hipStream_t stream) {
   const int block = 256;
   int64_t want = (total + block - 1) / block;
   int grid = (int)i64min(want, 256 * 8);
@@ -107,21 +109,19 @@ void launch_fused_adam(uintptr_t* params, uintptr_t* grads, uintptr_t* ms,
   HIP_CHECK_LAST();
 }
 
-template void launch_fused_adam<float>(uintptr_t*, uintptr_t*, uintptr_t*,
-                                       uintptr_t*, const int64_t*, int,
-                                       int64_t, float, float, float, float,
-                                       float, float, float, int,
-                                       hipStream_t);
-template void launch_fused_adam<__hip_bfloat16>(
+template void ddlb::launch_fused_adam<float>(
     uintptr_t*, uintptr_t*, uintptr_t*, uintptr_t*, const int64_t*, int,
-    int64_t, float, float, float, float, float, float, float, int,
-    hipStream_t);
+    int64_t, float, float, float, float, float, float, float, int, hipStream_t);
+template void ddlb::launch_fused_adam<__hip_bfloat16>(
+    uintptr_t*, uintptr_t*, uintptr_t*, uintptr_t*, const int64_t*, int,
+    int64_t, float, float, float, float, float, float, float, int, hipStream_t);
 
 template <typename T>
-void launch_fused_sgd(uintptr_t* params, uintptr_t* grads, uintptr_t* moms,
-                      const int64_t* prefix, int n_tensors, int64_t total,
-                      float lr, float momentum, float wd, int first_step,
-                      hipStream_t stream) {
+void ddlb::launch_fused_sgd(uintptr_t* params, uintptr_t* grads,
+                            uintptr_t* moms, const int64_t* prefix,
+                            int n_tensors, int64_t total, float lr,
+                            float momentum, float wd, int first_step,
+                            hipStream_t stream) {
   const int block = 256;
   int64_t want = (total + block - 1) / block;
   // >> 256 workgroups to fill 256 CUs / 8 XCDs; cap and grid-stride.
@@ -133,10 +133,9 @@ void launch_fused_sgd(uintptr_t* params, uintptr_t* grads, uintptr_t* moms,
   HIP_CHECK_LAST();
 }
 
-template void launch_fused_sgd<float>(uintptr_t*, uintptr_t*, uintptr_t*,
-                                      const int64_t*, int, int64_t, float,
-                                      float, float, int, hipStream_t);
-template void launch_fused_sgd<__hip_bfloat16>(uintptr_t*, uintptr_t*,
-                                               uintptr_t*, const int64_t*,
-                                               int, int64_t, float, float,
-                                               float, int, hipStream_t);
+template void ddlb::launch_fused_sgd<float>(
+    uintptr_t*, uintptr_t*, uintptr_t*, const int64_t*, int, int64_t, float,
+    float, float, int, hipStream_t);
+template void ddlb::launch_fused_sgd<__hip_bfloat16>(
+    uintptr_t*, uintptr_t*, uintptr_t*, const int64_t*, int, int64_t, float,
+    float, float, int, hipStream_t);

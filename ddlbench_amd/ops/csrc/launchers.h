@@ -1,0 +1,113 @@
+// Host entry points of the kernel files, declared once. bindings.hip
+// calls them; every .hip that defines one includes this header and
+// defines it under its qualified name (ddlb::launch_x), so a definition
+// whose signature drifts from the declaration does not compile.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace ddlb {
+
+// ---- fused_sgd.hip ----------------------------------------------------
+template <typename T>
+void launch_fused_sgd(uintptr_t* params, uintptr_t* grads, uintptr_t* moms,
+                      const int64_t* prefix, int n_tensors, int64_t total,
+                      float lr, float momentum, float wd, int first_step,
+                      hipStream_t stream);
+template <typename T>
+void launch_fused_adam(uintptr_t* params, uintptr_t* grads, uintptr_t* ms,
+                       uintptr_t* vs, const int64_t* prefix, int n_tensors,
+                       int64_t total, float lr, float beta1, float beta2,
+                       float eps, float wd, float bc1, float bc2,
+                       int decoupled, hipStream_t stream);
+
+// ---- bn_act.hip -------------------------------------------------------
+void set_bn_variant(int v);
+int64_t bn_reduce_gridS(int64_t N, int64_t C, int64_t HW, int nhwc,
+                        int elsize);
+template <typename T>
+void launch_bn_stats(const T*, double*, int64_t, int64_t, int64_t, int64_t,
+                     int, hipStream_t);
+void launch_bn_finalize(double*, float*, float*, float*, float*,
+                        int64_t, int64_t, double, float, float,
+                        hipStream_t);
+template <typename T>
+bool launch_bn_apply(const T*, const T*, T*, const float*, const float*,
+                     const float*, const float*, unsigned char*, int64_t,
+                     int64_t, int64_t, int, int, hipStream_t);
+template <typename T>
+void launch_bn_bwd_reduce(const T*, const T*, const T*, const float*,
+                          const float*, double*, const unsigned char*,
+                          int64_t, int64_t, int64_t, int64_t,
+                          int, int, hipStream_t);
+void launch_bn_bwd_finalize(double*, const float*, const float*,
+                            float*, float*, float*, int64_t, int64_t,
+                            double, int, hipStream_t);
+template <typename T>
+void launch_bn_bwd_dx(const T*, const T*, const T*, const float*,
+                      const float*, const float*, T*, T*,
+                      const unsigned char*, int64_t, int64_t,
+                      int64_t, int, int, hipStream_t);
+
+// ---- cross_entropy.hip ------------------------------------------------
+template <typename T>
+void launch_ce_fwd(const T*, const int64_t*, float*, float*, int64_t,
+                   int64_t, hipStream_t);
+template <typename T>
+void launch_ce_bwd(const T*, const int64_t*, const float*, const float*, T*,
+                   int64_t, int64_t, hipStream_t);
+
+// ---- conv_mfma.hip: forward (dgrad=0) or data-grad (dgrad=1); the dims
+// are always those of the forward conv --------------------------------
+void launch_conv_igemm(const void* a, const void* b, void* out,
+                       const void* zero, int N, int H, int W, int Cin,
+                       int K, int OH, int OW, int R, int S, int stride,
+                       int pad, int dgrad, hipStream_t stream);
+
+// ---- conv_wgrad.hip: part_ws holds part_cap floats of slab workspace ---
+void launch_conv_wgrad(const void* x, const void* dy, float* dw,
+                       float* part_ws, long part_cap, const void* zero,
+                       int N, int H, int W, int C, int K, int OH, int OW,
+                       int R, int S, int stride, int pad,
+                       hipStream_t stream);
+
+// ---- conv_stem.hip ----------------------------------------------------
+void launch_conv_stem_fwd(const void* x, const void* w, void* y, int N,
+                          int H, int W, int C, int K, int OH, int OW, int R,
+                          int stride, int pad, hipStream_t stream);
+void launch_conv_stem_wgrad(const void* x, const void* dy, float* dw,
+                            float* part, int N, int H, int W, int C, int K,
+                            int OH, int OW, int R, int stride, int pad,
+                            hipStream_t stream);
+int conv_stem_wgrad_chunks(int N, int OH, int OW, int K);
+
+// ---- maxpool.hip ------------------------------------------------------
+void launch_maxpool_fwd(const void*, void*, unsigned char*, int64_t,
+                        int64_t, int, int, int, int, int, int, int,
+                        hipStream_t);
+void launch_maxpool_bwd(const void*, const unsigned char*, void*,
+                        int64_t, int64_t, int, int, int, int, int, int,
+                        int, hipStream_t);
+
+// ---- seq_utils.hip ----------------------------------------------------
+template <typename T>
+void launch_revert_varlen(const T*, T*, const int64_t*, int64_t, int64_t,
+                          int64_t, hipStream_t);
+void launch_varlen_mask(const int64_t*, uint8_t*, int64_t, int64_t,
+                        hipStream_t);
+
+// ---- depthwise_conv.hip -----------------------------------------------
+template <typename T>
+void launch_dw3x3_fwd(const T*, const float*, T*, int64_t, int64_t, int64_t,
+                      int64_t, int64_t, int64_t, int, int, hipStream_t);
+template <typename T>
+void launch_dw3x3_bwd_dx(const T*, const float*, T*, int64_t, int64_t,
+                         int64_t, int64_t, int64_t, int64_t, int, int,
+                         hipStream_t);
+template <typename T>
+void launch_dw3x3_bwd_dw(const T*, const T*, double*, int64_t, int64_t,
+                         int64_t, int64_t, int64_t, int64_t, int, int,
+                         hipStream_t);
+
+}  // namespace ddlb

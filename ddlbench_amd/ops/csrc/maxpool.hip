@@ -10,6 +10,7 @@
 // atomics, no zero-init scatter.
 
 #include "common.h"
+#include "launchers.h"
 #include <stdint.h>
 #include <stdexcept>
 #include <string>
@@ -153,10 +154,10 @@ static void mp_geom(int64_t rows, int64_t C, int& CG8, int64_t& cblocks,
   S = i64min(i64max(rows / 16, 1), i64max(2048 / cblocks, 1));
 }
 
-void launch_maxpool_fwd(const void* x, void* y, unsigned char* idx,
-                        int64_t N, int64_t C, int H, int W, int OH,
-                        int OW, int k, int stride, int pad,
-                        hipStream_t stream) {
+void ddlb::launch_maxpool_fwd(const void* x, void* y, unsigned char* idx,
+                              int64_t N, int64_t C, int H, int W, int OH,
+                              int OW, int k, int stride, int pad,
+                              hipStream_t stream) {
   int CG8;
   int64_t cblocks, S;
   mp_geom(N * OH * OW, C, CG8, cblocks, S);
@@ -166,10 +167,10 @@ void launch_maxpool_fwd(const void* x, void* y, unsigned char* idx,
   HIP_CHECK_LAST();
 }
 
-void launch_maxpool_bwd(const void* dy, const unsigned char* idx,
-                        void* dx, int64_t N, int64_t C, int H, int W,
-                        int OH, int OW, int k, int stride, int pad,
-                        hipStream_t stream) {
+void ddlb::launch_maxpool_bwd(const void* dy, const unsigned char* idx,
+                              void* dx, int64_t N, int64_t C, int H, int W,
+                              int OH, int OW, int k, int stride, int pad,
+                              hipStream_t stream) {
   int CG8;
   int64_t cblocks, S;
   mp_geom(N * H * W, C, CG8, cblocks, S);

@@ -13,6 +13,7 @@
 // a host round trip per minibatch).
 
 #include "common.h"
+#include "launchers.h"
 #include <stdint.h>
 #include <stdexcept>
 #include <string>
@@ -56,9 +57,9 @@ static inline int seq_grid(int64_t total, int block) {
 }
 
 template <typename T>
-void launch_revert_varlen(const T* in, T* out, const int64_t* lengths,
-                          int64_t Tm, int64_t B, int64_t F,
-                          hipStream_t stream) {
+void ddlb::launch_revert_varlen(const T* in, T* out, const int64_t* lengths,
+                                int64_t Tm, int64_t B, int64_t F,
+                                hipStream_t stream) {
   const int block = 256;
   hipLaunchKernelGGL((revert_varlen_kernel<T>),
                      dim3(seq_grid(Tm * B * F, block)), dim3(block), 0,
@@ -66,17 +67,17 @@ void launch_revert_varlen(const T* in, T* out, const int64_t* lengths,
   HIP_CHECK_LAST();
 }
 
-void launch_varlen_mask(const int64_t* lengths, uint8_t* mask, int64_t Tm,
-                        int64_t B, hipStream_t stream) {
+void ddlb::launch_varlen_mask(const int64_t* lengths, uint8_t* mask, int64_t Tm,
+                              int64_t B, hipStream_t stream) {
   const int block = 256;
   hipLaunchKernelGGL(varlen_mask_kernel, dim3(seq_grid(Tm * B, block)),
                      dim3(block), 0, stream, lengths, mask, Tm, B);
   HIP_CHECK_LAST();
 }
 
-template void launch_revert_varlen<float>(const float*, float*,
-                                          const int64_t*, int64_t, int64_t,
-                                          int64_t, hipStream_t);
-template void launch_revert_varlen<__hip_bfloat16>(
-    const __hip_bfloat16*, __hip_bfloat16*, const int64_t*, int64_t,
-    int64_t, int64_t, hipStream_t);
+template void ddlb::launch_revert_varlen<float>(
+    const float*, float*, const int64_t*, int64_t, int64_t, int64_t,
+    hipStream_t);
+template void ddlb::launch_revert_varlen<__hip_bfloat16>(
+    const __hip_bfloat16*, __hip_bfloat16*, const int64_t*, int64_t, int64_t,
+    int64_t, hipStream_t);

@@ -222,6 +222,7 @@ def test_depthwise_conv(dtype, tol, stride):
     (2, 128, 9, 9, 512, 1, 1, 0),       # v2 fwd 4 column blocks
     (2, 256, 9, 9, 96, 3, 2, 1),        # v2 dgrad parity classes
     (2, 96, 16, 16, 96, 1, 1, 0),       # v2, Kd=96 (not mult of 64)
+    (2, 16, 10, 10, 16, 3, 3, 1),       # stride-3 dgrad: 128-tile gather
 ])
 def test_conv_mfma_fwd_dgrad(shape):
     from ddlbench_amd.ops.conv import conv2d_mfma
@@ -410,7 +411,7 @@ def test_model_trains_on_native_kernels():
     (3, 96, 13, 13, 104, 3, 1, 1),
     (2, 128, 9, 9, 512, 1, 1, 0),
     (2, 256, 10, 10, 128, 3, 2, 1),
-    (3, 64, 19, 19, 64, 3, 1, 1),    # narrow (512x64 combined-B) variant
+    (3, 64, 19, 19, 64, 3, 1, 1),    # narrow (256x64 combined-B) variant
     (2, 64, 10, 10, 56, 1, 1, 0),    # narrow, Nd=56 tail
 ])
 def test_conv_v2_matches_v1(shape):
