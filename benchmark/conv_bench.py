@@ -6,6 +6,12 @@ channels_last) and prints one JSON line per shape with ms and effective
 TFLOP/s for both backends — the measurement that drives the conv
 dispatch policy.
 
+Each row also carries the residual-join columns: ``mfma2_dgrad_add_ms``
+is the data-grad with the shortcut's gradient summed in its epilogue
+(``conv_igemm_dgrad(..., add=g)``), ``mfma2_dgrad_then_add_ms`` the plain
+data-grad followed by the torch bf16 add it replaces. ``--join`` prints
+only those (plus the plain data-grad) per shape.
+
 ``--stem`` instead times the small-C stem convs the model zoo builds
 (native csrc/conv_stem.hip vs the library), forward and weight-grad."""
 
@@ -120,6 +126,27 @@ def bench_stem(args):
         print(json.dumps(res), flush=True)
 
 
+def join_columns(ext, dy, w_perm, x, stride, pad, args):
+    """dgrad+add: fused epilogue addend vs dgrad followed by a torch add
+    (deep-pipeline structure; g stands in for the shortcut's gradient)."""
+    N, C, H, W = x.shape
+    g = torch.randn_like(x)
+    os.environ["DDLB_CONV_V2"] = "1"
+    fns = {
+        "mfma2_dgrad_add_ms": lambda: ext.conv_igemm_dgrad(
+            dy, w_perm, N, C, H, W, stride, pad, add=g),
+        "mfma2_dgrad_then_add_ms": lambda: ext.conv_igemm_dgrad(
+            dy, w_perm, N, C, H, W, stride, pad) + g,
+    }
+    # the two alternate; two passes, the lower time counts
+    best = {}
+    for _ in range(2):
+        for name, fn in fns.items():
+            t = bench_op(fn, args.iters, args.warmup)
+            best[name] = min(best.get(name, t), t)
+    return {k: round(t * 1e3, 3) for k, t in best.items()}
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--batch", type=int, default=256)
@@ -128,6 +155,9 @@ def main():
     p.add_argument("--stem", action="store_true",
                    help="time the model zoo's stem convs (native vs "
                         "library, forward and weight-grad) instead")
+    p.add_argument("--join", action="store_true",
+                   help="per shape, only the data-grad and the dgrad+add "
+                        "columns (fused addend vs dgrad then torch add)")
     args = p.parse_args()
     assert torch.cuda.is_available()
     torch.backends.cudnn.benchmark = True
@@ -155,6 +185,15 @@ def main():
         ext = require_extension()
         res = {"shape": f"C{C}_HW{HW}_K{K}_R{R}_s{stride}",
                "batch": N}
+        if args.join:
+            os.environ["DDLB_CONV_V2"] = "1"
+            t = bench_op(lambda: ext.conv_igemm_dgrad(
+                dy, w_perm, N, C, HW, HW, stride, pad),
+                args.iters, args.warmup)
+            res["mfma2_dgrad_ms"] = round(t * 1e3, 3)
+            res.update(join_columns(ext, dy, w_perm, x, stride, pad, args))
+            print(json.dumps(res), flush=True)
+            continue
         # forward: v2 (deep pipeline, default), v1 (128-tile), MIOpen
         os.environ["DDLB_CONV_V2"] = "1"
         t = bench_op(lambda: ext.conv_igemm_fwd(x, w, stride, pad),
@@ -189,6 +228,7 @@ def main():
             [0, 0], 1, [True, False, False]), args.iters, args.warmup)
         res["miopen_dgrad_ms"] = round(t * 1e3, 3)
         res["miopen_dgrad_tf"] = round(flops / t / 1e12, 1)
+        res.update(join_columns(ext, dy, w_perm, x, stride, pad, args))
         # wgrad: the transpose-read kernel (key name kept from the rows
         # that also timed the retired scalar-gather kernel as mfma_wgrad)
         t = bench_op(lambda: ext.conv_igemm_wgrad(x, dy, R, R, stride,

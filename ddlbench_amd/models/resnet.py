@@ -13,6 +13,7 @@ of three."""
 
 from __future__ import annotations
 
+import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
@@ -38,6 +39,16 @@ class Downsample(nn.Module):
         return self.bn(self.conv(x))
 
 
+def _joins(conv1, x):
+    """True when ``conv1`` is a native conv offering ``forward_join`` and
+    ``x`` is a bf16 device tensor: the block then takes its shortcut from
+    the conv's second output, which routes the shortcut's gradient
+    through the conv's autograd node so the block input's two gradients
+    are summed inside the data-grad kernel."""
+    return (hasattr(conv1, "forward_join") and x.is_cuda
+            and x.dtype == torch.bfloat16)
+
+
 class BasicBlock(nn.Module):
     expansion = 1
 
@@ -52,8 +63,14 @@ class BasicBlock(nn.Module):
             self.downsample = Downsample(cin, planes * self.expansion, stride)
 
     def forward(self, x):
-        identity = x if self.downsample is None else self.downsample(x)
-        out = self.bn1(self.conv1(x))
+        if _joins(self.conv1, x):
+            out, skip = self.conv1.forward_join(x)
+            identity = (skip if self.downsample is None
+                        else self.downsample(skip))
+            out = self.bn1(out)
+        else:
+            identity = x if self.downsample is None else self.downsample(x)
+            out = self.bn1(self.conv1(x))
         return self.bn2(self.conv2(out), res=identity)
 
 
@@ -80,8 +97,14 @@ class Bottleneck(nn.Module):
             self.downsample = Downsample(cin, planes * self.expansion, stride)
 
     def forward(self, x):
-        identity = x if self.downsample is None else self.downsample(x)
-        out = self.bn1(self.conv1(x))
+        if _joins(self.conv1, x):
+            out, skip = self.conv1.forward_join(x)
+            identity = (skip if self.downsample is None
+                        else self.downsample(skip))
+            out = self.bn1(out)
+        else:
+            identity = x if self.downsample is None else self.downsample(x)
+            out = self.bn1(self.conv1(x))
         out = self.bn2(self.conv2(out))
         return self.bn3(self.conv3(out), res=identity)
 

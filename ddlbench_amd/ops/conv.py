@@ -36,6 +36,32 @@ def _dw_to_weight_layout(dw32, weight):
     return dw32.view(K, R, S, C).permute(0, 3, 1, 2).to(weight.dtype)
 
 
+def _conv_backward(ctx, dy, add=None):
+    """dx (+ add, fused into the dgrad epilogue) and dw of a native conv."""
+    ext = _ops.require_extension()
+    x, weight = ctx.saved_tensors
+    dy = dy.contiguous(memory_format=_CL)
+    dx = dw = None
+    if ctx.needs_input_grad[0]:
+        # (K,C,R,S) logical -> (C,R,S,K) memory for the dgrad B tile
+        w_perm = weight.permute(1, 2, 3, 0).contiguous()
+        dx = ext.conv_igemm_dgrad(dy, w_perm, x.size(0), x.size(1),
+                                  x.size(2), x.size(3), ctx.stride,
+                                  ctx.pad, add)
+    if ctx.needs_input_grad[1]:
+        if _WGRAD == "mfma":
+            dw = _dw_to_weight_layout(
+                ext.conv_igemm_wgrad(x, dy, weight.shape[2],
+                                     weight.shape[3], ctx.stride,
+                                     ctx.pad), weight)
+        else:
+            dw = torch.ops.aten.convolution_backward(
+                dy, x, weight, None, [ctx.stride, ctx.stride],
+                [ctx.pad, ctx.pad], [1, 1], False, [0, 0], 1,
+                [False, True, False])[1]
+    return dx, dw
+
+
 class _ConvMFMA(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, stride, pad):
@@ -50,32 +76,49 @@ class _ConvMFMA(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        ext = _ops.require_extension()
-        x, weight = ctx.saved_tensors
-        dy = dy.contiguous(memory_format=_CL)
-        dx = dw = None
-        if ctx.needs_input_grad[0]:
-            # (K,C,R,S) logical -> (C,R,S,K) memory for the dgrad B tile
-            w_perm = weight.permute(1, 2, 3, 0).contiguous()
-            dx = ext.conv_igemm_dgrad(dy, w_perm, x.size(0), x.size(1),
-                                      x.size(2), x.size(3), ctx.stride,
-                                      ctx.pad)
-        if ctx.needs_input_grad[1]:
-            if _WGRAD == "mfma":
-                dw = _dw_to_weight_layout(
-                    ext.conv_igemm_wgrad(x, dy, weight.shape[2],
-                                         weight.shape[3], ctx.stride,
-                                         ctx.pad), weight)
-            else:
-                dw = torch.ops.aten.convolution_backward(
-                    dy, x, weight, None, [ctx.stride, ctx.stride],
-                    [ctx.pad, ctx.pad], [1, 1], False, [0, 0], 1,
-                    [False, True, False])[1]
+        dx, dw = _conv_backward(ctx, dy)
         return dx, dw, None, None
 
 
 def conv2d_mfma(x, weight, stride=1, pad=0):
     return _ConvMFMA.apply(x, weight, stride, pad)
+
+
+class _ConvMFMAJoin(torch.autograd.Function):
+    """Conv at a residual fork: returns ``(y, x)`` — the conv output and
+    the input passed through as the shortcut's source (an alias, no copy).
+    Both gradients that meet at ``x`` then arrive at this one node, and
+    the backward hands the shortcut's to the dgrad kernel as its epilogue
+    addend instead of leaving a separate bf16 add to autograd. The caller
+    guarantees ``x`` is channels_last (``Conv2dMFMA.forward_join``), so
+    nothing beyond what ``_ConvMFMA`` saves is kept alive."""
+
+    @staticmethod
+    def forward(ctx, x, weight, stride, pad):
+        ext = _ops.require_extension()
+        w = weight.contiguous(memory_format=_CL)
+        y = ext.conv_igemm_fwd(x, w, stride, pad)
+        ctx.save_for_backward(x, weight)
+        ctx.stride = stride
+        ctx.pad = pad
+        # an unused shortcut arrives as dskip=None, not as a zero tensor
+        ctx.set_materialize_grads(False)
+        return y, x
+
+    @staticmethod
+    def backward(ctx, dy, dskip):
+        if dy is None:
+            # only the shortcut was used: its gradient passes through
+            return dskip, None, None, None
+        if dskip is not None:
+            dskip = dskip.contiguous(memory_format=_CL)
+        dx, dw = _conv_backward(ctx, dy, dskip)
+        return dx, dw, None, None
+
+
+def join_enabled() -> bool:
+    """DDLB_JOIN=0 (read per call) restores the unfused residual join."""
+    return os.environ.get("DDLB_JOIN", "1") != "0"
 
 
 def mfma_eligible(conv: nn.Conv2d, x_dtype=torch.bfloat16) -> bool:
@@ -127,6 +170,18 @@ class Conv2dMFMA(_NativeConv2d):
 
     def native(self, x):
         return conv2d_mfma(x, self.weight, self.stride, self.padding)
+
+    def forward_join(self, x):
+        """``(conv(x), skip)`` for a block whose input also feeds its
+        shortcut: take the shortcut from ``skip`` and the two gradients
+        meeting at ``x`` are summed in the dgrad epilogue. Inputs the
+        fused path does not cover (not a channels_last bf16 device
+        tensor, or DDLB_JOIN=0) get the plain conv and ``x`` itself."""
+        if (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4
+                and x.is_contiguous(memory_format=_CL) and join_enabled()):
+            return _ConvMFMAJoin.apply(x, self.weight, self.stride,
+                                       self.padding)
+        return self.forward(x), x
 
 
 class _ConvStem(torch.autograd.Function):

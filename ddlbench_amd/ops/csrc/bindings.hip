@@ -288,17 +288,35 @@ torch::Tensor conv_igemm_fwd(torch::Tensor x, torch::Tensor w,
   auto y = empty_nhwc(x, N, K, OH, OW);
   launch_conv_igemm(x.data_ptr(), w.data_ptr(), y.data_ptr(),
                     zero_page(x).data_ptr(), N, H, W, C, K, OH, OW, R, S,
-                    (int)stride, (int)pad, /*dgrad=*/0, cur_stream());
+                    (int)stride, (int)pad, /*dgrad=*/0, /*add=*/nullptr,
+                    cur_stream());
   return y;
 }
 
 // dy: (N,K,OH,OW) channels_last; w_perm: (C,R,S,K) plain-contiguous
-// memory (host permutes once per backward). Returns channels_last dx.
+// memory (the autograd bridge permutes the weight once per backward
+// call). Returns a freshly allocated channels_last dx.
+// add: optional (N,C,H,W) channels_last bf16 tensor — the other gradient
+// meeting dx at a residual join. It is only read; the result equals
+// dgrad(dy) + add bit for bit (the accumulator is rounded to bf16, then
+// one bf16 add). The kernels' epilogues do the add wherever every dx
+// element is written exactly once; the one case that relies on a
+// pre-zeroed dx (stride 2 with R==1 or S==1) adds after the launch.
 torch::Tensor conv_igemm_dgrad(torch::Tensor dy, torch::Tensor w_perm,
                                int64_t N, int64_t C, int64_t H, int64_t W,
-                               int64_t stride, int64_t pad) {
+                               int64_t stride, int64_t pad,
+                               c10::optional<torch::Tensor> add) {
   check_conv_operand(dy, "dy", "conv_igemm");
   TORCH_CHECK(w_perm.is_contiguous(), "w_perm must be contiguous");
+  if (add) {
+    check_conv_operand(*add, "add", "conv_igemm");
+    TORCH_CHECK(add->dim() == 4 && add->size(0) == N &&
+                    add->size(1) == C && add->size(2) == H &&
+                    add->size(3) == W,
+                "add must have dx's shape (N,C,H,W)");
+    TORCH_CHECK(add->device() == dy.device(),
+                "add must be on dy's device");
+  }
   const int K = dy.size(1), OH = dy.size(2), OW = dy.size(3);
   const int R = w_perm.size(1), S = w_perm.size(2);
   TORCH_CHECK(K % 8 == 0, "conv_igemm dgrad needs K % 8 == 0");
@@ -307,11 +325,14 @@ torch::Tensor conv_igemm_dgrad(torch::Tensor dy, torch::Tensor w_perm,
   // (zero_() after empty: torch::zeros does not honour the
   // channels_last memory_format request)
   auto dx = empty_nhwc(dy, N, C, H, W);
-  if (stride == 2 && (R == 1 || S == 1)) dx.zero_();
+  const bool sparse = stride == 2 && (R == 1 || S == 1);
+  if (sparse) dx.zero_();
   launch_conv_igemm(dy.data_ptr(), w_perm.data_ptr(), dx.data_ptr(),
                     zero_page(dy).data_ptr(), (int)N, (int)H, (int)W,
                     (int)C, K, OH, OW, R, S, (int)stride, (int)pad,
-                    /*dgrad=*/1, cur_stream());
+                    /*dgrad=*/1, add && !sparse ? add->data_ptr() : nullptr,
+                    cur_stream());
+  if (add && sparse) dx.add_(*add);
   return dx;
 }
 
@@ -529,7 +550,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_igemm_fwd", &conv_igemm_fwd,
         "NHWC bf16 MFMA implicit-GEMM conv forward");
   m.def("conv_igemm_dgrad", &conv_igemm_dgrad,
-        "NHWC bf16 MFMA implicit-GEMM conv data-grad");
+        "NHWC bf16 MFMA implicit-GEMM conv data-grad (+ optional addend)",
+        py::arg("dy"), py::arg("w_perm"), py::arg("N"), py::arg("C"),
+        py::arg("H"), py::arg("W"), py::arg("stride"), py::arg("pad"),
+        py::arg("add") = py::none());
   m.def("conv_igemm_wgrad", &conv_igemm_wgrad,
         "NHWC bf16 MFMA implicit-GEMM conv weight-grad (fp32 out)");
   m.def("conv_stem_fwd", &conv_stem_fwd,

@@ -106,7 +106,9 @@ DEV const bf16* b_chunk_addr(const ConvParams& p, long row, long kkg) {
 // Tile geometry is templated so small output-channel counts get a
 // narrow N tile instead of half-empty MFMA work: 4 waves arranged
 // (WR x WC) each owning a (BM_/WR x BN_/WC) sub-tile.
-template <int MODE, int BM_, int BN_, int WR, int WC>
+// ADD: dgrad epilogue adds p.add (same rounding order as the deep-pipeline
+// kernel: round the accumulator to bf16, then one bf16 add).
+template <int MODE, int BM_, int BN_, int WR, int WC, bool ADD>
 __global__ __launch_bounds__(THREADS, 2)
 void conv_igemm_kernel(ConvParams p) {
   constexpr int WM = BM_ / WR;        // wave tile M
@@ -235,8 +237,12 @@ void conv_igemm_kernel(ConvParams p) {
 #pragma unroll
       for (int nf = 0; nf < NF; ++nf) {
         const long col = bn + wn + nf * 16 + fr;
-        if (col < p.Nd)
-          p.out[out_row * p.Nd + col] = from_f32<bf16>(acc[mf][nf][reg]);
+        if (col < p.Nd) {
+          const long o = out_row * p.Nd + col;
+          bf16 v = from_f32<bf16>(acc[mf][nf][reg]);
+          if (ADD) v = from_f32<bf16>(to_f32(v) + to_f32(p.add[o]));
+          p.out[o] = v;
+        }
       }
     }
   }
@@ -246,12 +252,20 @@ void conv_igemm_kernel(ConvParams p) {
 void ddlb::launch_conv_igemm(const void* a, const void* b, void* out,
                              const void* zero, int N, int H, int W, int Cin,
                              int K, int OH, int OW, int R, int S, int stride,
-                             int pad, int dgrad, hipStream_t stream) {
+                             int pad, int dgrad, const void* add,
+                             hipStream_t stream) {
+  // the addend needs every dx element written exactly once: FPROP has
+  // no addend, and stride-2 classes with R==1 or S==1 leave pixels to
+  // the caller's zero fill (the binding adds after the launch there)
+  if (add && (!dgrad || (stride == 2 && K % 8 == 0 && (R == 1 || S == 1))))
+    throw std::invalid_argument(
+        "launch_conv_igemm: addend unsupported for this pass");
   ConvParams p;
   p.a = (const bf16*)a;
   p.b = (const bf16*)b;
   p.out = (bf16*)out;
   p.zero = (const bf16*)zero;
+  p.add = (const bf16*)add;
   p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.K = K; p.OH = OH; p.OW = OW;
   p.R = R; p.S = S; p.stride = stride; p.pad = pad;
   if (!dgrad) {
@@ -269,9 +283,16 @@ void ddlb::launch_conv_igemm(const void* a, const void* b, void* out,
     const long nbm = (p.M + (BM_) - 1) / (BM_);                             \
     const long nbn = (p.Nd + (BN_) - 1) / (BN_);                            \
     const size_t lds_bytes = 2 * ((BM_) + (BN_)) * BK * sizeof(bf16);       \
-    hipLaunchKernelGGL((conv_igemm_kernel<MODE, BM_, BN_, WR, WC>),         \
-                       dim3((unsigned)(nbm * nbn)), dim3(THREADS),          \
-                       lds_bytes, stream, p);                               \
+    if ((MODE) != 0 && p.add)                                               \
+      hipLaunchKernelGGL(                                                   \
+          (conv_igemm_kernel<MODE, BM_, BN_, WR, WC, (MODE) != 0>),         \
+          dim3((unsigned)(nbm * nbn)), dim3(THREADS), lds_bytes, stream,    \
+          p);                                                               \
+    else                                                                    \
+      hipLaunchKernelGGL(                                                   \
+          (conv_igemm_kernel<MODE, BM_, BN_, WR, WC, false>),               \
+          dim3((unsigned)(nbm * nbn)), dim3(THREADS), lds_bytes, stream,    \
+          p);                                                               \
   } while (0)
 #define LAUNCH_TILED(MODE)                                                  \
   do {                                                                      \

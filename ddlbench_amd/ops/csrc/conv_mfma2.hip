@@ -168,7 +168,10 @@ DEV const bf16* b_slot_addr(const ConvParams& p, const Cursor& cu,
 // k0, waves 4-7 fill k1) and B's cursor advances by 64.
 // LIN: 1x1 stride-1 pad-0 conv — the implicit-GEMM A operand is the
 // plain row-major tensor (no im2col arithmetic, no bounds tests)
-template <int MODE, int BM_, int BN_, int WR, int WC, bool LIN>
+// ADD: the dgrad epilogue adds p.add (the residual join's other
+// gradient) to the bf16-rounded tile before the store; ADD=false is the
+// plain kernel, instruction for instruction.
+template <int MODE, int BM_, int BN_, int WR, int WC, bool LIN, bool ADD>
 __global__ __launch_bounds__(THREADS2, 2)
 void conv_igemm2_kernel(ConvParams p) {
   constexpr int WM = BM_ / WR;       // wave tile M
@@ -355,6 +358,32 @@ void conv_igemm2_kernel(ConvParams p) {
   static_assert((long)BM_ * BN_ * 2 <= 4L * (BM_ + BN_) * 32 * 2,
                 "tile image must fit the staging LDS");
   {
+    constexpr int CPR = BN_ / 8;            // 16-B chunks per tile row
+    constexpr int ITERS = BM_ * CPR / THREADS2;
+    typedef __attribute__((ext_vector_type(8))) unsigned short u16x8;
+    // ADD: the addend chunks this thread will store over depend only on
+    // tid, so their loads are issued here — ahead of the image write and
+    // its barrier — and land behind the LDS round trip. The staging
+    // state and fragments are dead by now; ITERS*4 VGPRs fit under the
+    // main loop's peak.
+    u16x8 addv[ADD ? ITERS : 1];
+    if (ADD) {
+#pragma unroll
+      for (int it = 0; it < ITERS; ++it) {
+        const int idx = it * THREADS2 + tid;
+        const int r = idx / CPR;
+        const int ck = idx - r * CPR;
+        const long row = bm + r;
+        const long colbase = bn + ck * 8;
+        addv[it] = u16x8{0, 0, 0, 0, 0, 0, 0, 0};
+        if (row < p.M && colbase + 8 <= p.Nd) {
+          const long out_row =
+              (MODE == 2) ? conv_class_dx_row(p, row) : row;
+          addv[it] = *reinterpret_cast<const u16x8*>(
+              p.add + out_row * p.Nd + colbase);
+        }
+      }
+    }
     bf16* img = lds;
 #pragma unroll
     for (int mf = 0; mf < MF; ++mf)
@@ -365,9 +394,6 @@ void conv_igemm2_kernel(ConvParams p) {
           img[(awoff + mf * 16 + fk * 4 + reg) * BN_ +
               bwoff + nf * 16 + fr] = from_f32<bf16>(acc[mf][nf][reg]);
     __syncthreads();
-    constexpr int CPR = BN_ / 8;            // 16-B chunks per tile row
-    constexpr int ITERS = BM_ * CPR / THREADS2;
-    typedef __attribute__((ext_vector_type(8))) unsigned short u16x8;
 #pragma unroll
     for (int it = 0; it < ITERS; ++it) {
       const int idx = it * THREADS2 + tid;
@@ -380,11 +406,21 @@ void conv_igemm2_kernel(ConvParams p) {
       const long colbase = bn + ck * 8;
       const bf16* src = img + r * BN_ + ck * 8;
       if (colbase + 8 <= p.Nd) {
-        *reinterpret_cast<u16x8*>(p.out + out_row * p.Nd + colbase) =
-            *reinterpret_cast<const u16x8*>(src);
+        u16x8 v = *reinterpret_cast<const u16x8*>(src);
+        if (ADD) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            v[j] = conv_bf16_add_bits(v[j], addv[it][j]);
+        }
+        *reinterpret_cast<u16x8*>(p.out + out_row * p.Nd + colbase) = v;
       } else if (colbase < p.Nd) {
-        for (int j = 0; j < (int)(p.Nd - colbase); ++j)
-          p.out[out_row * p.Nd + colbase + j] = src[j];
+        for (int j = 0; j < (int)(p.Nd - colbase); ++j) {
+          const long o = out_row * p.Nd + colbase + j;
+          if (ADD)
+            p.out[o] = from_f32<bf16>(to_f32(src[j]) + to_f32(p.add[o]));
+          else
+            p.out[o] = src[j];
+        }
       }
     }
   }
@@ -395,9 +431,19 @@ void launch_tile(const ConvParams& p, hipStream_t stream) {
   const long nbm = (p.M + BM_ - 1) / BM_;
   const long nbn = (p.Nd + BN_ - 1) / BN_;
   const size_t lds_bytes = 4 * (BM_ + BN_) * 32 * sizeof(bf16);
-  hipLaunchKernelGGL((conv_igemm2_kernel<MODE, BM_, BN_, WR, WC, LIN>),
-                     dim3((unsigned)(nbm * nbn)), dim3(THREADS2), lds_bytes,
-                     stream, p);
+  // the addend variant exists for the dgrad modes only
+  if constexpr (MODE != 0) {
+    if (p.add) {
+      hipLaunchKernelGGL(
+          (conv_igemm2_kernel<MODE, BM_, BN_, WR, WC, LIN, true>),
+          dim3((unsigned)(nbm * nbn)), dim3(THREADS2), lds_bytes, stream,
+          p);
+      return;
+    }
+  }
+  hipLaunchKernelGGL(
+      (conv_igemm2_kernel<MODE, BM_, BN_, WR, WC, LIN, false>),
+      dim3((unsigned)(nbm * nbn)), dim3(THREADS2), lds_bytes, stream, p);
 }
 
 // High-occupancy tiles (116-122 VGPR -> 4 waves/SIMD, <= 80 KiB LDS ->

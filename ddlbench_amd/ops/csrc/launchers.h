@@ -59,11 +59,14 @@ void launch_ce_bwd(const T*, const int64_t*, const float*, const float*, T*,
                    int64_t, int64_t, hipStream_t);
 
 // ---- conv_mfma.hip: forward (dgrad=0) or data-grad (dgrad=1); the dims
-// are always those of the forward conv --------------------------------
+// are always those of the forward conv. add (dgrad only, nullptr = none)
+// is a read-only bf16 tensor of dx's geometry summed into dx in the
+// epilogue; stride-2 with R==1 or S==1 does not take one (throws) ------
 void launch_conv_igemm(const void* a, const void* b, void* out,
                        const void* zero, int N, int H, int W, int Cin,
                        int K, int OH, int OW, int R, int S, int stride,
-                       int pad, int dgrad, hipStream_t stream);
+                       int pad, int dgrad, const void* add,
+                       hipStream_t stream);
 
 // ---- conv_wgrad.hip: part_ws holds part_cap floats of slab workspace ---
 void launch_conv_wgrad(const void* x, const void* dy, float* dw,
