@@ -95,6 +95,29 @@ int conv_out_size(int64_t H, int64_t pad, int64_t R, int64_t stride) {
   return (int)((H + 2 * pad - R) / stride + 1);
 }
 
+// geometry contract of the conv_igemm bindings and plan queries; checked
+// first, so a violation raises before any size is derived or launched on
+void check_conv_geometry(const char* op, int64_t N, int64_t H, int64_t W,
+                         int64_t R, int64_t S, int64_t stride,
+                         int64_t pad) {
+  TORCH_CHECK(stride >= 1, op, ": stride must be >= 1");
+  TORCH_CHECK(pad >= 0, op, ": pad must be >= 0");
+  TORCH_CHECK(R >= 1 && S >= 1, op, ": kernel dims must be >= 1");
+  TORCH_CHECK(N >= 1 && H >= 1 && W >= 1, op, ": empty input");
+  TORCH_CHECK(H + 2 * pad >= R && W + 2 * pad >= S, op,
+              ": kernel larger than the padded input");
+}
+
+// dy's (N, OH, OW) against the forward conv's geometry
+void check_conv_dy(const char* op, const torch::Tensor& dy, int64_t N,
+                   int64_t H, int64_t W, int64_t R, int64_t S,
+                   int64_t stride, int64_t pad) {
+  TORCH_CHECK(dy.size(0) == N, op, ": dy batch does not match x");
+  TORCH_CHECK(dy.size(2) == conv_out_size(H, pad, R, stride) &&
+                  dy.size(3) == conv_out_size(W, pad, S, stride),
+              op, ": dy spatial dims do not match (H,W,R,S,stride,pad)");
+}
+
 torch::Tensor empty_nhwc(const torch::Tensor& like, int64_t N, int64_t C,
                          int64_t H, int64_t W) {
   return torch::empty({N, C, H, W}, like.options().memory_format(
@@ -278,11 +301,16 @@ torch::Tensor ce_bwd(torch::Tensor logits, torch::Tensor target,
 // channels_last memory (= (K,R,S,C) image). Returns channels_last y.
 torch::Tensor conv_igemm_fwd(torch::Tensor x, torch::Tensor w,
                              int64_t stride, int64_t pad) {
+  TORCH_CHECK(x.dim() == 4 && w.dim() == 4, "conv_igemm: 4-D tensors only");
   check_conv_operand(x, "x", "conv_igemm");
   check_conv_operand(w, "w", "conv_igemm");
+  TORCH_CHECK(w.device() == x.device(), "conv_igemm: w must be on x's device");
   const int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   const int K = w.size(0), R = w.size(2), S = w.size(3);
+  TORCH_CHECK(w.size(1) == C, "conv_igemm: weight C does not match x");
   TORCH_CHECK(C % 8 == 0, "conv_igemm fwd needs C % 8 == 0");
+  TORCH_CHECK(K >= 1, "conv_igemm: empty weight");
+  check_conv_geometry("conv_igemm", N, H, W, R, S, stride, pad);
   const int OH = conv_out_size(H, pad, R, stride);
   const int OW = conv_out_size(W, pad, S, stride);
   auto y = empty_nhwc(x, N, K, OH, OW);
@@ -306,7 +334,12 @@ torch::Tensor conv_igemm_dgrad(torch::Tensor dy, torch::Tensor w_perm,
                                int64_t N, int64_t C, int64_t H, int64_t W,
                                int64_t stride, int64_t pad,
                                c10::optional<torch::Tensor> add) {
+  TORCH_CHECK(dy.dim() == 4 && w_perm.dim() == 4,
+              "conv_igemm: 4-D tensors only");
   check_conv_operand(dy, "dy", "conv_igemm");
+  TORCH_CHECK(w_perm.is_cuda() && w_perm.scalar_type() == at::kBFloat16 &&
+                  w_perm.device() == dy.device(),
+              "conv_igemm: w_perm must be a bf16 tensor on dy's device");
   TORCH_CHECK(w_perm.is_contiguous(), "w_perm must be contiguous");
   if (add) {
     check_conv_operand(*add, "add", "conv_igemm");
@@ -320,6 +353,10 @@ torch::Tensor conv_igemm_dgrad(torch::Tensor dy, torch::Tensor w_perm,
   const int K = dy.size(1), OH = dy.size(2), OW = dy.size(3);
   const int R = w_perm.size(1), S = w_perm.size(2);
   TORCH_CHECK(K % 8 == 0, "conv_igemm dgrad needs K % 8 == 0");
+  TORCH_CHECK(C >= 1 && w_perm.size(0) == C && w_perm.size(3) == K,
+              "conv_igemm: w_perm must be (C,R,S,K) for dx's C and dy's K");
+  check_conv_geometry("conv_igemm", N, H, W, R, S, stride, pad);
+  check_conv_dy("conv_igemm", dy, N, H, W, R, S, stride, pad);
   // stride-2 parity classes with R==1 or S==1 have pixel classes no tap
   // reaches — those dx entries must be zeros, so zero-init in that case
   // (zero_() after empty: torch::zeros does not honour the
@@ -342,23 +379,83 @@ torch::Tensor conv_igemm_dgrad(torch::Tensor dy, torch::Tensor w_perm,
 torch::Tensor conv_igemm_wgrad(torch::Tensor x, torch::Tensor dy,
                                int64_t R, int64_t S, int64_t stride,
                                int64_t pad) {
+  TORCH_CHECK(x.dim() == 4 && dy.dim() == 4, "conv_wgrad: 4-D tensors only");
   check_conv_operand(x, "x", "conv_wgrad");
   check_conv_operand(dy, "dy", "conv_wgrad");
+  TORCH_CHECK(dy.device() == x.device(),
+              "conv_wgrad: dy must be on x's device");
   const int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   const int K = dy.size(1), OH = dy.size(2), OW = dy.size(3);
   TORCH_CHECK(C % 8 == 0 && K % 8 == 0,
               "conv_wgrad needs C %% 8 == 0 and K %% 8 == 0");
+  TORCH_CHECK(K >= 1, "conv_wgrad: empty dy");
+  check_conv_geometry("conv_wgrad", N, H, W, R, S, stride, pad);
+  check_conv_dy("conv_wgrad", dy, N, H, W, R, S, stride, pad);
   auto dw = torch::empty({K, R * S * C},
                          x.options().dtype(at::kFloat));
   // split-P partial-slab workspace: a fixed 8M floats (32 MB), the
   // launcher caps its split to fit
   static WsCache wgws;
-  auto part = cached_ws(wgws, x, at::kFloat, 8 << 20);
+  auto part = cached_ws(wgws, x, at::kFloat, kConvWgradPartCap);
   launch_conv_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr<float>(),
                     part.data_ptr<float>(), (long)part.numel(),
                     zero_page(x).data_ptr(), N, H, W, C, K, OH, OW, (int)R,
                     (int)S, (int)stride, (int)pad, cur_stream());
   return dw;
+}
+
+// ---- dispatch plans ---------------------------------------------------
+// The launchers' own host decisions for a shape (no device needed): the
+// functions below call exactly what launch_conv_igemm / launch_conv_wgrad
+// call, so a test can assert which kernel variant a shape reaches.
+// One dict per launch (up to four parity classes for stride-2 dgrad);
+// honours DDLB_CONV_V2 like the launcher.
+py::list conv_igemm_plan_py(int64_t N, int64_t C, int64_t H, int64_t W,
+                            int64_t K, int64_t R, int64_t S, int64_t stride,
+                            int64_t pad, bool dgrad) {
+  check_conv_geometry("conv_igemm_plan", N, H, W, R, S, stride, pad);
+  const ConvIgemmPlan plan = conv_igemm_plan(
+      (int)N, (int)H, (int)W, (int)C, (int)K,
+      conv_out_size(H, pad, R, stride), conv_out_size(W, pad, S, stride),
+      (int)R, (int)S, (int)stride, (int)pad, dgrad ? 1 : 0);
+  py::list out;
+  for (int i = 0; i < plan.n; ++i) {
+    const ConvIgemmLaunch& e = plan.e[i];
+    py::dict d;
+    d["structure"] = e.v2 ? "v2" : "v1";
+    d["mode"] = e.mode;
+    d["BM"] = e.bm;
+    d["BN"] = e.bn;
+    d["LIN"] = e.lin != 0;
+    d["M"] = e.M;
+    d["Nd"] = e.Nd;
+    d["Kd"] = e.Kd;
+    d["cls"] = py::make_tuple(e.cls_a, e.cls_b);
+    d["taps"] = py::make_tuple(e.nr, e.ns);
+    out.append(d);
+  }
+  return out;
+}
+
+py::dict conv_wgrad_plan_py(int64_t N, int64_t C, int64_t H, int64_t W,
+                            int64_t K, int64_t R, int64_t S, int64_t stride,
+                            int64_t pad) {
+  check_conv_geometry("conv_wgrad_plan", N, H, W, R, S, stride, pad);
+  const ConvWgradPlan pl = conv_wgrad_plan(
+      (int)N, (int)C, (int)K, conv_out_size(H, pad, R, stride),
+      conv_out_size(W, pad, S, stride), (int)R, (int)S, (int)stride,
+      (int)pad, kConvWgradPartCap);
+  py::dict d;
+  d["TK"] = pl.tk;
+  d["TR"] = pl.tr;
+  d["ring"] = pl.ring;
+  d["r1"] = pl.r1 != 0;
+  d["split"] = pl.split;
+  d["p_per"] = pl.p_per;
+  d["steps"] = pl.steps;
+  d["tail"] = pl.tail;
+  d["psb"] = pl.psb;
+  return d;
 }
 
 // ---- stem conv (C < 8, NHWC bf16) -------------------------------------
@@ -556,6 +653,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("add") = py::none());
   m.def("conv_igemm_wgrad", &conv_igemm_wgrad,
         "NHWC bf16 MFMA implicit-GEMM conv weight-grad (fp32 out)");
+  m.def("conv_igemm_plan", &conv_igemm_plan_py,
+        "launches conv_igemm_fwd/dgrad make for a shape (host only)",
+        py::arg("N"), py::arg("C"), py::arg("H"), py::arg("W"),
+        py::arg("K"), py::arg("R"), py::arg("S"), py::arg("stride"),
+        py::arg("pad"), py::arg("dgrad"));
+  m.def("conv_wgrad_plan", &conv_wgrad_plan_py,
+        "tile/split/steps conv_igemm_wgrad uses for a shape (host only)",
+        py::arg("N"), py::arg("C"), py::arg("H"), py::arg("W"),
+        py::arg("K"), py::arg("R"), py::arg("S"), py::arg("stride"),
+        py::arg("pad"));
   m.def("conv_stem_fwd", &conv_stem_fwd,
         "NHWC bf16 MFMA stem conv (C < 8) forward");
   m.def("conv_stem_wgrad", &conv_stem_wgrad,

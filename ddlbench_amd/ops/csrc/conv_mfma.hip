@@ -249,6 +249,89 @@ void conv_igemm_kernel(ConvParams p) {
 }
 
 // ---- launchers --------------------------------------------------------
+namespace {
+
+// fills one plan entry from the prepared params: the deep-pipeline
+// structure (conv_mfma2.hip) first, else the 128-tile structure with a
+// narrow N tile for small output-channel counts
+void plan_entry(const ConvParams& p, int mode, bool use_v2,
+                ddlb::ConvIgemmLaunch& e) {
+  e.mode = mode;
+  e.M = p.M; e.Nd = p.Nd; e.Kd = p.Kd;
+  e.cls_a = e.cls_b = e.r0 = e.s0 = e.nr = e.ns = e.nh = e.nw = 0;
+  if (mode == 2) {
+    e.cls_a = p.cls_a; e.cls_b = p.cls_b; e.r0 = p.r0; e.s0 = p.s0;
+    e.nr = p.nr; e.ns = p.ns; e.nh = p.nh; e.nw = p.nw;
+  }
+  bool lin = false;
+  e.v2 = use_v2 && conv_igemm_v2_select(p, mode, e.bm, e.bn, lin);
+  e.lin = lin;
+  if (e.v2) return;
+  if (p.Nd <= 64 && p.M >= 256) { e.bm = 256; e.bn = 64; }
+  else if (p.Nd <= 64) { e.bm = 128; e.bn = 64; }
+  else { e.bm = 128; e.bn = 128; }
+}
+
+// the dims every pass shares; M/Nd/Kd are those of the whole pass
+// (stride-2 dgrad overrides M and Kd per parity class)
+void fill_dims(ConvParams& p, int N, int H, int W, int Cin, int K, int OH,
+               int OW, int R, int S, int stride, int pad, int dgrad) {
+  p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.K = K; p.OH = OH; p.OW = OW;
+  p.R = R; p.S = S; p.stride = stride; p.pad = pad;
+  if (!dgrad) {
+    p.M = (long)N * OH * OW;
+    p.Nd = K;
+    p.Kd = (long)R * S * Cin;
+  } else {
+    p.M = (long)N * H * W;
+    p.Nd = Cin;
+    p.Kd = (long)R * S * K;
+  }
+}
+
+}  // namespace
+
+ddlb::ConvIgemmPlan ddlb::conv_igemm_plan(int N, int H, int W, int Cin,
+                                          int K, int OH, int OW, int R,
+                                          int S, int stride, int pad,
+                                          int dgrad) {
+  ConvParams p{};
+  fill_dims(p, N, H, W, Cin, K, OH, OW, R, S, stride, pad, dgrad);
+  // deep-pipeline structure (conv_mfma2.hip) first; DDLB_CONV_V2=0
+  // forces the 128-tile structure (re-read per call so benchmarks can
+  // A/B the two structures in one process)
+  const char* v2e = getenv("DDLB_CONV_V2");
+  const bool use_v2 = !(v2e && v2e[0] == '0');
+
+  ConvIgemmPlan plan;
+  plan.n = 0;
+  if (!dgrad) {
+    plan_entry(p, 0, use_v2, plan.e[plan.n++]);
+  } else if (stride == 2 && K % 8 == 0) {
+    // four parity classes, each a dense reduction over its valid taps
+    for (int a_ = 0; a_ < 2; ++a_) {
+      for (int b_ = 0; b_ < 2; ++b_) {
+        p.cls_a = a_;
+        p.cls_b = b_;
+        // r valid iff (ih + pad - r) even  ->  r ≡ (a_ + pad) (mod 2)
+        p.r0 = (a_ + pad) & 1;
+        p.s0 = (b_ + pad) & 1;
+        p.nr = (R - p.r0 + 1) / 2;
+        p.ns = (S - p.s0 + 1) / 2;
+        p.nh = (H - a_ + 1) / 2;
+        p.nw = (W - b_ + 1) / 2;
+        if (p.nr <= 0 || p.ns <= 0 || p.nh <= 0 || p.nw <= 0) continue;
+        p.M = (long)N * p.nh * p.nw;
+        p.Kd = (long)p.nr * p.ns * K;
+        plan_entry(p, 2, use_v2, plan.e[plan.n++]);
+      }
+    }
+  } else {
+    plan_entry(p, 1, use_v2, plan.e[plan.n++]);
+  }
+  return plan;
+}
+
 void ddlb::launch_conv_igemm(const void* a, const void* b, void* out,
                              const void* zero, int N, int H, int W, int Cin,
                              int K, int OH, int OW, int R, int S, int stride,
@@ -266,17 +349,7 @@ void ddlb::launch_conv_igemm(const void* a, const void* b, void* out,
   p.out = (bf16*)out;
   p.zero = (const bf16*)zero;
   p.add = (const bf16*)add;
-  p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.K = K; p.OH = OH; p.OW = OW;
-  p.R = R; p.S = S; p.stride = stride; p.pad = pad;
-  if (!dgrad) {
-    p.M = (long)N * OH * OW;
-    p.Nd = K;
-    p.Kd = (long)R * S * Cin;
-  } else {
-    p.M = (long)N * H * W;
-    p.Nd = Cin;
-    p.Kd = (long)R * S * K;
-  }
+  fill_dims(p, N, H, W, Cin, K, OH, OW, R, S, stride, pad, dgrad);
 
 #define LAUNCH(MODE, BM_, BN_, WR, WC)                                      \
   do {                                                                      \
@@ -296,41 +369,23 @@ void ddlb::launch_conv_igemm(const void* a, const void* b, void* out,
   } while (0)
 #define LAUNCH_TILED(MODE)                                                  \
   do {                                                                      \
-    if (p.Nd <= 64 && p.M >= 256) LAUNCH(MODE, 256, 64, 4, 1);              \
-    else if (p.Nd <= 64) LAUNCH(MODE, 128, 64, 4, 1);                       \
+    if (e.bm == 256) LAUNCH(MODE, 256, 64, 4, 1);                           \
+    else if (e.bn == 64) LAUNCH(MODE, 128, 64, 4, 1);                       \
     else LAUNCH(MODE, 128, 128, 2, 2);                                      \
   } while (0)
 
-  // deep-pipeline structure (conv_mfma2.hip) first; DDLB_CONV_V2=0
-  // forces the 128-tile structure (re-read per call so benchmarks can
-  // A/B the two structures in one process)
-  const char* v2e = getenv("DDLB_CONV_V2");
-  const bool use_v2 = !(v2e && v2e[0] == '0');
-
-  if (!dgrad) {
-    if (!(use_v2 && launch_conv_igemm_v2(p, 0, stream))) LAUNCH_TILED(0);
-  } else if (stride == 2 && K % 8 == 0) {
-    // four parity classes, each a dense reduction over its valid taps
-    for (int a_ = 0; a_ < 2; ++a_) {
-      for (int b_ = 0; b_ < 2; ++b_) {
-        p.cls_a = a_;
-        p.cls_b = b_;
-        // r valid iff (ih + pad - r) even  ->  r ≡ (a_ + pad) (mod 2)
-        p.r0 = (a_ + pad) & 1;
-        p.s0 = (b_ + pad) & 1;
-        p.nr = (R - p.r0 + 1) / 2;
-        p.ns = (S - p.s0 + 1) / 2;
-        p.nh = (H - a_ + 1) / 2;
-        p.nw = (W - b_ + 1) / 2;
-        if (p.nr <= 0 || p.ns <= 0 || p.nh <= 0 || p.nw <= 0) continue;
-        p.M = (long)N * p.nh * p.nw;
-        p.Kd = (long)p.nr * p.ns * K;
-        if (!(use_v2 && launch_conv_igemm_v2(p, 2, stream)))
-          LAUNCH_TILED(2);
-      }
-    }
-  } else {
-    if (!(use_v2 && launch_conv_igemm_v2(p, 1, stream))) LAUNCH_TILED(1);
+  const ConvIgemmPlan plan = conv_igemm_plan(N, H, W, Cin, K, OH, OW, R, S,
+                                             stride, pad, dgrad);
+  for (int i = 0; i < plan.n; ++i) {
+    const ConvIgemmLaunch& e = plan.e[i];
+    p.M = e.M;
+    p.Kd = e.Kd;
+    p.cls_a = e.cls_a; p.cls_b = e.cls_b; p.r0 = e.r0; p.s0 = e.s0;
+    p.nr = e.nr; p.ns = e.ns; p.nh = e.nh; p.nw = e.nw;
+    if (e.v2) launch_conv_igemm_v2(p, e.mode, e.bm, e.lin != 0, stream);
+    else if (e.mode == 0) LAUNCH_TILED(0);
+    else if (e.mode == 1) LAUNCH_TILED(1);
+    else LAUNCH_TILED(2);
   }
 #undef LAUNCH_TILED
 #undef LAUNCH

@@ -451,30 +451,30 @@ void launch_tile(const ConvParams& p, hipStream_t stream) {
 // 256-row tile pays in parked waves. Nd >= 96 tiles 128x128 with column
 // blocks; Nd in [48, 96) gets the 256x64 combined-B tile.
 template <int MODE, bool LIN>
-bool dispatch_tile(const ConvParams& p, hipStream_t stream) {
-  if (p.Nd >= 96)
+void dispatch_tile(const ConvParams& p, int bm, hipStream_t stream) {
+  if (bm == 128)
     launch_tile<MODE, 128, 128, 2, 4, LIN>(p, stream);
-  else if (p.Nd >= 48)
-    launch_tile<MODE, 256, 64, 4, 2, LIN>(p, stream);
   else
-    return false;
-  return true;
+    launch_tile<MODE, 256, 64, 4, 2, LIN>(p, stream);
 }
 
 template <int MODE>
-bool dispatch_v2(const ConvParams& p, hipStream_t stream) {
+void dispatch_v2(const ConvParams& p, int bm, bool lin,
+                 hipStream_t stream) {
   // the parity-class gather (MODE 2) is never a plain row-major operand
   if constexpr (MODE != 2) {
-    if (p.R == 1 && p.S == 1 && p.stride == 1 && p.pad == 0)
-      return dispatch_tile<MODE, true>(p, stream);
+    if (lin) {
+      dispatch_tile<MODE, true>(p, bm, stream);
+      return;
+    }
   }
-  return dispatch_tile<MODE, false>(p, stream);
+  dispatch_tile<MODE, false>(p, bm, stream);
 }
 
 }  // namespace
 
-bool launch_conv_igemm_v2(const ConvParams& p, int mode,
-                          hipStream_t stream) {
+bool conv_igemm_v2_select(const ConvParams& p, int mode, int& bm, int& bn,
+                          bool& lin) {
   // staging offsets are 32-bit; MODE 1 is stride-1 only (stride-2
   // dgrad goes through the MODE-2 parity classes)
   const long a_elems = (mode == 0)
@@ -485,13 +485,26 @@ bool launch_conv_igemm_v2(const ConvParams& p, int mode,
                            : p.Nd * p.Kd;
   if (a_elems >= (1L << 31) || b_elems >= (1L << 31)) return false;
   if (mode == 1 && p.stride != 1) return false;
-  bool ok;
+  if (p.Nd >= 96) {
+    bm = 128;
+    bn = 128;
+  } else if (p.Nd >= 48) {
+    bm = 256;
+    bn = 64;
+  } else {
+    return false;
+  }
+  lin = mode != 2 && p.R == 1 && p.S == 1 && p.stride == 1 && p.pad == 0;
+  return true;
+}
+
+void launch_conv_igemm_v2(const ConvParams& p, int mode, int bm, bool lin,
+                          hipStream_t stream) {
   if (mode == 0)
-    ok = dispatch_v2<0>(p, stream);
+    dispatch_v2<0>(p, bm, lin, stream);
   else if (mode == 1)
-    ok = dispatch_v2<1>(p, stream);
+    dispatch_v2<1>(p, bm, lin, stream);
   else
-    ok = dispatch_v2<2>(p, stream);
-  if (ok) HIP_CHECK_LAST();
-  return ok;
+    dispatch_v2<2>(p, bm, lin, stream);
+  HIP_CHECK_LAST();
 }

@@ -326,6 +326,38 @@ void wg_launch(const WgradParams& q, bool r1, unsigned grid, size_t lds,
 
 }  // namespace
 
+ddlb::ConvWgradPlan ddlb::conv_wgrad_plan(int N, int C, int K, int OH,
+                                          int OW, int R, int S, int stride,
+                                          int pad, long part_cap) {
+  ConvWgradPlan pl;
+  const long P = (long)N * OH * OW;
+  const long RSC = (long)R * S * C;
+  // tile by shape: square 128 where possible (least re-staging),
+  // rectangular when only one dim allows it
+  const bool bigK = K >= 128, bigR = RSC >= 128;
+  pl.tk = bigK ? 128 : 64;
+  pl.tr = bigR ? 128 : 64;
+  pl.nk = (K + pl.tk - 1) / pl.tk;
+  pl.nr = (RSC + pl.tr - 1) / pl.tr;
+  long split = 2048 / i64max(pl.nk * pl.nr, 1);
+  split = i64max(i64min(split, (P + WG_BKP - 1) / WG_BKP), 1);
+  split = i64min(split, 256);  // combine traffic cap
+  if (split > 1)
+    split = i64min(split, part_cap / i64max((long)K * RSC, 1));
+  split = i64max(split, 1);
+  pl.split = split;
+  // square tile: 512 threads on a 2-buffer ring (64 KiB, 2 blocks/CU);
+  // smaller tiles: 256 threads on the 3-buffer ring
+  pl.ring = (bigK && bigR) ? 2 : 3;
+  pl.r1 = (R == 1 && S == 1 && stride == 1 && pad == 0);
+  // the kernel's chunking: chunk i covers [i*p_per, min((i+1)*p_per, P))
+  pl.p_per = (P + split - 1) / split;
+  pl.steps = (pl.p_per + WG_BKP - 1) / WG_BKP;
+  pl.tail = pl.p_per - (pl.steps - 1) * WG_BKP;
+  pl.psb = split > 1 ? (split + 63) / 64 : 0;
+  return pl;
+}
+
 void ddlb::launch_conv_wgrad(const void* x, const void* dy, float* dw,
                              float* part_ws, long part_cap, const void* zero,
                              int N, int H, int W, int C, int K, int OH, int OW,
@@ -342,34 +374,24 @@ void ddlb::launch_conv_wgrad(const void* x, const void* dy, float* dw,
   q.P = (long)N * OH * OW;
   q.RSC = (long)R * S * C;
 
-  // tile by shape: square 128 where possible (least re-staging),
-  // rectangular when only one dim allows it
-  const bool bigK = K >= 128, bigR = q.RSC >= 128;
-  const long TKt = bigK ? 128 : 64, TRt = bigR ? 128 : 64;
-  const long nk = (K + TKt - 1) / TKt;
-  const long nr = (q.RSC + TRt - 1) / TRt;
-  long split = 2048 / i64max(nk * nr, 1);
-  split = i64max(i64min(split, (q.P + WG_BKP - 1) / WG_BKP), 1);
-  split = i64min(split, 256);  // combine traffic cap
-  if (split > 1)
-    split = i64min(split, part_cap / i64max(q.K * q.RSC, 1));
-  split = i64max(split, 1);
-  q.split_p = (int)split;
-  const bool bigsq = bigK && bigR;
-  const size_t lds =
-      (bigsq ? 2 : 3) * WG_BKP * (TKt + TRt) * sizeof(bf16);
-  // square tile: 512 threads on a 2-buffer ring (64 KiB, 2 blocks/CU);
-  // smaller tiles: 256 threads on the 3-buffer ring
-  const bool r1 = (R == 1 && S == 1 && stride == 1 && pad == 0);
-  const unsigned grid = (unsigned)(nk * nr * q.split_p);
-  if (bigsq) wg_launch<128, 128, 2, 4, 512, true>(q, r1, grid, lds, stream);
-  else if (bigR) wg_launch<64, 128, 1, 4, 256, false>(q, r1, grid, lds, stream);
-  else if (bigK) wg_launch<128, 64, 4, 1, 256, false>(q, r1, grid, lds, stream);
-  else wg_launch<64, 64, 1, 4, 256, false>(q, r1, grid, lds, stream);
+  const ConvWgradPlan pl = conv_wgrad_plan(N, C, K, OH, OW, R, S, stride,
+                                           pad, part_cap);
+  q.split_p = (int)pl.split;
+  const size_t lds = pl.ring * WG_BKP * (pl.tk + pl.tr) * sizeof(bf16);
+  const bool r1 = pl.r1 != 0;
+  const unsigned grid = (unsigned)(pl.nk * pl.nr * q.split_p);
+  if (pl.tk == 128 && pl.tr == 128)
+    wg_launch<128, 128, 2, 4, 512, true>(q, r1, grid, lds, stream);
+  else if (pl.tr == 128)
+    wg_launch<64, 128, 1, 4, 256, false>(q, r1, grid, lds, stream);
+  else if (pl.tk == 128)
+    wg_launch<128, 64, 4, 1, 256, false>(q, r1, grid, lds, stream);
+  else
+    wg_launch<64, 64, 1, 4, 256, false>(q, r1, grid, lds, stream);
   if (q.split_p > 1) {
     const long total = q.K * q.RSC;
     const int blocks = (int)i64min((total + 255) / 256, 2048);
-    const int psb = (q.split_p + 63) / 64;
+    const int psb = (int)pl.psb;
     // multi-chunk combine accumulates with atomics -> dw must be 0
     // (dw arrives as torch::empty; the single-chunk combine writes)
     if (psb > 1)

@@ -68,7 +68,44 @@ void launch_conv_igemm(const void* a, const void* b, void* out,
                        int pad, int dgrad, const void* add,
                        hipStream_t stream);
 
+// The launches launch_conv_igemm makes for a shape, as pure host data:
+// the launcher walks this plan, and the bindings expose it so tests can
+// assert which kernel variant a shape reaches.
+struct ConvIgemmLaunch {
+  int v2;      // 1 = deep-pipeline structure (conv_mfma2.hip), 0 = 128-tile
+  int mode;    // 0 FPROP, 1 DGRAD gather, 2 DGRAD stride-2 parity class
+  int bm, bn;  // block tile
+  int lin;     // v2 only: plain row-major A operand (1x1 stride-1 pad-0)
+  long M, Nd, Kd;                            // GEMM dims of this launch
+  int cls_a, cls_b, r0, s0, nr, ns, nh, nw;  // mode 2 only, else 0
+};
+struct ConvIgemmPlan {
+  int n;                 // launches: 1, or up to 4 parity classes
+  ConvIgemmLaunch e[4];
+};
+// reads DDLB_CONV_V2 at call time, as the launcher always has
+ConvIgemmPlan conv_igemm_plan(int N, int H, int W, int Cin, int K, int OH,
+                              int OW, int R, int S, int stride, int pad,
+                              int dgrad);
+
 // ---- conv_wgrad.hip: part_ws holds part_cap floats of slab workspace ---
+// floats of split-P slab workspace the binding hands launch_conv_wgrad
+constexpr long kConvWgradPartCap = 8L << 20;
+// launch_conv_wgrad's host decisions for a shape
+struct ConvWgradPlan {
+  int tk, tr;    // dw tile (k rows x rsc columns)
+  int ring;      // LDS ring depth: 2 for the 128x128 tile, else 3
+  int r1;        // 1x1 stride-1 pad-0: linear B operand, no carry chain
+  long nk, nr;   // tiles along k and rsc
+  long split;    // p-chunks per tile (grid = nk*nr*split)
+  long p_per;    // pixels per chunk (the last chunk may hold fewer)
+  long steps;    // 64-pixel steps of a full chunk
+  long tail;     // pixels in a full chunk's last step (64 = not ragged)
+  long psb;      // combine rows: 0 no combine (split == 1), 1 plain
+                 // stores, > 1 memset + atomicAdd
+};
+ConvWgradPlan conv_wgrad_plan(int N, int C, int K, int OH, int OW, int R,
+                              int S, int stride, int pad, long part_cap);
 void launch_conv_wgrad(const void* x, const void* dy, float* dw,
                        float* part_ws, long part_cap, const void* zero,
                        int N, int H, int W, int C, int K, int OH, int OW,
