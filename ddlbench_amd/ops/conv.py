@@ -26,6 +26,13 @@ from ddlbench_amd import ops as _ops
 # DDLB_WGRAD=library opts back into aten's conv backward
 _WGRAD = os.environ.get("DDLB_WGRAD", "mfma")
 
+# The backward's layout/dtype tail runs in native kernels: the dgrad
+# weight layout is one tiled transpose (conv_weight_dgrad_layout) and the
+# weight-grad kernels write the weight's dtype and layout themselves
+# (conv_igemm_wgrad_bf16). False restores the eager-tensor tail (a strided
+# permute copy, fp32 dw + cast) — same values, kept for comparison.
+NATIVE_TAIL = os.environ.get("DDLB_CONV_TAIL", "native") != "eager"
+
 _CL = torch.channels_last
 
 
@@ -44,12 +51,21 @@ def _conv_backward(ctx, dy, add=None):
     dx = dw = None
     if ctx.needs_input_grad[0]:
         # (K,C,R,S) logical -> (C,R,S,K) memory for the dgrad B tile
-        w_perm = weight.permute(1, 2, 3, 0).contiguous()
+        if NATIVE_TAIL and (weight.is_contiguous(memory_format=_CL)
+                            or weight.is_contiguous()):
+            w_perm = ext.conv_weight_dgrad_layout(weight)
+        else:
+            w_perm = weight.permute(1, 2, 3, 0).contiguous()
         dx = ext.conv_igemm_dgrad(dy, w_perm, x.size(0), x.size(1),
                                   x.size(2), x.size(3), ctx.stride,
                                   ctx.pad, add)
     if ctx.needs_input_grad[1]:
-        if _WGRAD == "mfma":
+        if _WGRAD == "mfma" and NATIVE_TAIL \
+                and weight.dtype == torch.bfloat16:
+            dw = ext.conv_igemm_wgrad_bf16(x, dy, weight.shape[2],
+                                           weight.shape[3], ctx.stride,
+                                           ctx.pad)
+        elif _WGRAD == "mfma":
             dw = _dw_to_weight_layout(
                 ext.conv_igemm_wgrad(x, dy, weight.shape[2],
                                      weight.shape[3], ctx.stride,

@@ -70,15 +70,32 @@ torch::Tensor zero_page(const torch::Tensor& like) {
   return cached_ws(zp, like, at::kBFloat16, 16, 0, /*zeroed=*/true);
 }
 
-// BN reduction workspace: [S][2][C] double partial slabs.
-// Reduce-style kernels write plain per-block stores and the finalize
-// kernels sum over S — no cross-block atomics (a C=64 layer at S~1500
-// slices serialized ~1500 f64 atomics per channel address), and no
-// zeroing (every slab slot is written every call).
-torch::Tensor bn_sums_workspace(const torch::Tensor& like, int64_t C,
-                                int64_t S) {
-  static WsCache ws;
-  return cached_ws(ws, like, at::kDouble, 2 * C * S, 1 << 18);
+// BN reduce + finalize workspaces, sized by bn_workspace_plan (the
+// launchers' own geometry decision).
+// sums: [S][2][C] partial slabs, fp32 or double by plan. Reduce-style
+// kernels write plain per-block stores and the finalize kernel sums over
+// S — no cross-block atomics (a C=64 layer at S~1500 slices serialized
+// ~1500 f64 atomics per channel address), and no zeroing (every slab slot
+// is written every call).
+// part / tickets: the finalize kernel's second-level partials and its
+// per-channel-chunk ticket words. The tickets are zeroed once, at
+// allocation; each launch leaves them at zero.
+struct BnWorkspace {
+  BnWorkspacePlan plan;
+  torch::Tensor sums, part, tickets;
+};
+BnWorkspace bn_workspace(const torch::Tensor& x, int64_t N, int64_t C,
+                         int64_t HW, bool nhwc) {
+  static WsCache ws_sums, ws_part, ws_tickets;
+  BnWorkspace w;
+  w.plan = bn_workspace_plan(N, C, HW, nhwc, (int)x.element_size());
+  w.sums = cached_ws(ws_sums, x, at::kDouble, (w.plan.slab_bytes + 7) / 8,
+                     1 << 18);
+  w.part = cached_ws(ws_part, x, at::kDouble,
+                     std::max<int64_t>(w.plan.part_doubles, 1), 1 << 16);
+  w.tickets = cached_ws(ws_tickets, x, at::kInt, w.plan.cchunks, 1 << 10,
+                        /*zeroed=*/true);
+  return w;
 }
 
 // is_cuda + bf16 + channels_last, the operand contract of the conv and
@@ -174,16 +191,16 @@ std::vector<torch::Tensor> bn_act_fwd(
   torch::Tensor mean = torch::empty({C}, fopt);
   torch::Tensor invstd = torch::empty({C}, fopt);
   if (training) {
-    const int64_t S =
-        bn_reduce_gridS(N, C, HW, nhwc, (int)x.element_size());
-    torch::Tensor sums = bn_sums_workspace(x, C, S);
+    const BnWorkspace ws = bn_workspace(x, N, C, HW, nhwc);
+    const int64_t S = ws.plan.S;
     dispatch_f32_bf16(x, [&](auto tag) {
       using T = decltype(tag);
-      launch_bn_stats<T>(dptr<T>(x), dptr<double>(sums), N, C, HW, S, nhwc,
+      launch_bn_stats<T>(dptr<T>(x), ws.sums.data_ptr(), N, C, HW, S, nhwc,
                          s);
     });
     launch_bn_finalize(
-        dptr<double>(sums), dptr<float>(mean), dptr<float>(invstd),
+        ws.sums.data_ptr(), ws.plan.slab_f32, dptr<double>(ws.part),
+        dptr<unsigned>(ws.tickets), dptr<float>(mean), dptr<float>(invstd),
         running_mean ? dptr<float>(*running_mean) : nullptr,
         running_var ? dptr<float>(*running_var) : nullptr, C, S,
         (double)(N * HW), (float)eps, (float)momentum, s);
@@ -230,8 +247,8 @@ std::vector<torch::Tensor> bn_act_bwd(torch::Tensor dy,
   const int64_t N = x.size(0), C = x.size(1), HW = x.size(2) * x.size(3);
   auto s = cur_stream();
   auto fopt = x.options().dtype(at::kFloat);
-  const int64_t S = bn_reduce_gridS(N, C, HW, nhwc, (int)x.element_size());
-  torch::Tensor sums = bn_sums_workspace(x, C, S);
+  const BnWorkspace ws = bn_workspace(x, N, C, HW, nhwc);
+  const int64_t S = ws.plan.S;
   torch::Tensor dgamma = torch::empty({C}, fopt);
   torch::Tensor dbeta = torch::empty({C}, fopt);
   torch::Tensor k = torch::empty({3, C}, fopt);
@@ -250,9 +267,11 @@ std::vector<torch::Tensor> bn_act_bwd(torch::Tensor dy,
     using T = decltype(tag);
     const T* yp = y_opt ? dptr<T>(*y_opt) : nullptr;
     launch_bn_bwd_reduce<T>(dptr<T>(dy), yp, dptr<T>(x), dptr<float>(mean),
-                            dptr<float>(invstd), dptr<double>(sums), mp, N,
+                            dptr<float>(invstd), ws.sums.data_ptr(), mp, N,
                             C, HW, S, (int)act, nhwc, s);
-    launch_bn_bwd_finalize(dptr<double>(sums), dptr<float>(gamma),
+    launch_bn_bwd_finalize(ws.sums.data_ptr(), ws.plan.slab_f32,
+                           dptr<double>(ws.part), dptr<unsigned>(ws.tickets),
+                           dptr<float>(gamma),
                            dptr<float>(invstd), dptr<float>(dgamma),
                            dptr<float>(dbeta), dptr<float>(k), C, S,
                            (double)(N * HW), training, s);
@@ -374,11 +393,15 @@ torch::Tensor conv_igemm_dgrad(torch::Tensor dy, torch::Tensor w_perm,
 }
 
 // x: (N,C,H,W) channels_last; dy: (N,K,OH,OW) channels_last.
-// Returns fp32 dw in (K, R*S*C) memory = logical (K,C,R,S) channels_last
-// after the python-side permute.
-torch::Tensor conv_igemm_wgrad(torch::Tensor x, torch::Tensor dy,
-                               int64_t R, int64_t S, int64_t stride,
-                               int64_t pad) {
+// out_bf16 = false: fp32 dw in (K, R*S*C) memory = logical (K,C,R,S)
+// channels_last after the python-side permute. out_bf16 = true: a bf16
+// tensor of logical shape (K,C,R,S) with channels_last strides (the same
+// (K,R,S,C) memory), each element the round-to-nearest-even bf16 of its
+// fp32 sum, written by the kernels themselves.
+static torch::Tensor conv_wgrad_impl(const torch::Tensor& x,
+                                     const torch::Tensor& dy, int64_t R,
+                                     int64_t S, int64_t stride, int64_t pad,
+                                     bool out_bf16) {
   TORCH_CHECK(x.dim() == 4 && dy.dim() == 4, "conv_wgrad: 4-D tensors only");
   check_conv_operand(x, "x", "conv_wgrad");
   check_conv_operand(dy, "dy", "conv_wgrad");
@@ -391,17 +414,62 @@ torch::Tensor conv_igemm_wgrad(torch::Tensor x, torch::Tensor dy,
   TORCH_CHECK(K >= 1, "conv_wgrad: empty dy");
   check_conv_geometry("conv_wgrad", N, H, W, R, S, stride, pad);
   check_conv_dy("conv_wgrad", dy, N, H, W, R, S, stride, pad);
-  auto dw = torch::empty({K, R * S * C},
-                         x.options().dtype(at::kFloat));
+  // strides (R*S*C, 1, S*C, C): channels_last also where K, R or S is 1
+  auto dw = out_bf16
+                ? torch::empty({K, R, S, C}, x.options()).permute({0, 3, 1, 2})
+                : torch::empty({K, R * S * C}, x.options().dtype(at::kFloat));
   // split-P partial-slab workspace: a fixed 8M floats (32 MB), the
   // launcher caps its split to fit
   static WsCache wgws;
   auto part = cached_ws(wgws, x, at::kFloat, kConvWgradPartCap);
-  launch_conv_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr<float>(),
+  launch_conv_wgrad(x.data_ptr(), dy.data_ptr(),
+                    out_bf16 ? nullptr : dw.data_ptr<float>(),
                     part.data_ptr<float>(), (long)part.numel(),
                     zero_page(x).data_ptr(), N, H, W, C, K, OH, OW, (int)R,
-                    (int)S, (int)stride, (int)pad, cur_stream());
+                    (int)S, (int)stride, (int)pad, cur_stream(),
+                    out_bf16 ? dw.data_ptr() : nullptr);
   return dw;
+}
+
+torch::Tensor conv_igemm_wgrad(torch::Tensor x, torch::Tensor dy,
+                               int64_t R, int64_t S, int64_t stride,
+                               int64_t pad) {
+  return conv_wgrad_impl(x, dy, R, S, stride, pad, /*out_bf16=*/false);
+}
+
+torch::Tensor conv_igemm_wgrad_bf16(torch::Tensor x, torch::Tensor dy,
+                                    int64_t R, int64_t S, int64_t stride,
+                                    int64_t pad) {
+  return conv_wgrad_impl(x, dy, R, S, stride, pad, /*out_bf16=*/true);
+}
+
+// weight: bf16 logical (K,C,R,S), channels_last ((K,R,S,C) memory) or
+// plain contiguous. Returns the contiguous (C,R,S,K) tensor the dgrad
+// kernels read — a pure copy, equal to weight.permute(1,2,3,0).contiguous().
+torch::Tensor conv_weight_dgrad_layout(torch::Tensor weight) {
+  TORCH_CHECK(weight.is_cuda() && weight.scalar_type() == at::kBFloat16,
+              "conv_weight_dgrad_layout: bf16 HIP tensors only");
+  TORCH_CHECK(weight.dim() == 4,
+              "conv_weight_dgrad_layout: weight must be 4-D (K,C,R,S)");
+  const int64_t K = weight.size(0), C = weight.size(1);
+  const int64_t R = weight.size(2), S = weight.size(3);
+  TORCH_CHECK(K >= 8 && C >= 8 && K % 8 == 0 && C % 8 == 0 && R >= 1 &&
+                  S >= 1,
+              "conv_weight_dgrad_layout needs K % 8 == 0 and C % 8 == 0");
+  const bool cl = weight.is_contiguous(at::MemoryFormat::ChannelsLast);
+  TORCH_CHECK(cl || weight.is_contiguous(),
+              "conv_weight_dgrad_layout: weight must be channels_last or "
+              "contiguous");
+  auto out = torch::empty({C, R, S, K}, weight.options().memory_format(
+                                            at::MemoryFormat::Contiguous));
+  const int64_t RS = R * S;
+  if (cl)  // in[k][rs][c] -> out[c][rs][k], batch rs
+    launch_weight_transpose(weight.data_ptr(), out.data_ptr(), RS, K, C,
+                            RS * C, C, RS * K, K, cur_stream());
+  else     // in[k][c*rs] -> out[c*rs][k]: one plain 2-D transpose
+    launch_weight_transpose(weight.data_ptr(), out.data_ptr(), 1, K, C * RS,
+                            C * RS, 0, K, 0, cur_stream());
+  return out;
 }
 
 // ---- dispatch plans ---------------------------------------------------
@@ -653,6 +721,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("add") = py::none());
   m.def("conv_igemm_wgrad", &conv_igemm_wgrad,
         "NHWC bf16 MFMA implicit-GEMM conv weight-grad (fp32 out)");
+  m.def("conv_igemm_wgrad_bf16", &conv_igemm_wgrad_bf16,
+        "MFMA weight-grad straight to bf16 (K,C,R,S) channels_last",
+        py::arg("x"), py::arg("dy"), py::arg("R"), py::arg("S"),
+        py::arg("stride"), py::arg("pad"));
+  m.def("conv_weight_dgrad_layout", &conv_weight_dgrad_layout,
+        "bf16 weight (K,C,R,S) -> contiguous (C,R,S,K) for the dgrad kernels",
+        py::arg("weight"));
   m.def("conv_igemm_plan", &conv_igemm_plan_py,
         "launches conv_igemm_fwd/dgrad make for a shape (host only)",
         py::arg("N"), py::arg("C"), py::arg("H"), py::arg("W"),

@@ -124,10 +124,11 @@ __global__ void bn_stats_nhwc_kernel(const T* __restrict__ x,
 // ---- stats, NHWC vectorized: 8 channels (16 B) per lane --------------
 // Each thread covers channels c0..c0+7 of CG8*8-channel groups; f32
 // per-thread partials over a short row slice (<= a few hundred values)
-// combine in LDS across row-groups, then one f64 atomic per channel.
+// combine in LDS across row-groups and land in an fp32 slab (the values
+// never were wider than fp32).
 template <typename T>
 __global__ void bn_stats_nhwc_vec_kernel(const T* __restrict__ x,
-                                         double* __restrict__ sums,
+                                         float* __restrict__ sums,
                                          int64_t rows, int64_t C, int CG8) {
   typedef __attribute__((ext_vector_type(8))) short short8x;
   __shared__ float tmp[2][256][8];
@@ -171,8 +172,8 @@ __global__ void bn_stats_nhwc_vec_kernel(const T* __restrict__ x,
       }
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      sums[((int64_t)blockIdx.y * 2 + 0) * C + c0 + j] = (double)s[j];
-      sums[((int64_t)blockIdx.y * 2 + 1) * C + c0 + j] = (double)ss[j];
+      sums[((int64_t)blockIdx.y * 2 + 0) * C + c0 + j] = s[j];
+      sums[((int64_t)blockIdx.y * 2 + 1) * C + c0 + j] = ss[j];
     }
   }
 }
@@ -225,41 +226,160 @@ __global__ void bn_stats_nhwc_vec_f32_kernel(const float* __restrict__ x,
   }
 }
 
-// ---- finalize: mean/invstd + running-stat update ----------------------
-// sums = per-(row-slice) partial slabs [S][2][C] (the reduce kernels
-// write plain stores — a C=64 layer at S~1500 slices would otherwise
-// serialize ~1500 f64 atomics per channel address)
-// one block per channel; 1024 threads block-reduce the S slabs (the
-// C-bounded grid is the parallelism bottleneck at C=64/S~2048 — a
-// 256-thread block left the chip at 1 wave/CU reading 2 MB)
-__global__ void bn_finalize_kernel(const double* __restrict__ sums,
-                                   float* __restrict__ mean,
-                                   float* __restrict__ invstd,
-                                   float* __restrict__ running_mean,
-                                   float* __restrict__ running_var,
-                                   int64_t C, int64_t S, double count,
-                                   float eps, float momentum) {
-  __shared__ double tmp[16];
-  const int64_t c = blockIdx.x;
-  double s = 0.0, ss = 0.0;
-  for (int64_t b = threadIdx.x; b < S; b += blockDim.x) {
-    s += sums[(b * 2 + 0) * C + c];
-    ss += sums[(b * 2 + 1) * C + c];
+// ---- finalize: slabs -> per-channel results, one launch ----------------
+// sums = per-(row-slice) partial slabs [S][2][C] written with plain
+// stores by the reduce kernels (a C=64 layer at S~1500 slices would
+// otherwise serialize ~1500 f64 atomics per channel address). ST is the
+// slab element: float from the bf16 vec reduces, double from the scalar
+// and fp32 ones.
+//
+// Geometry: block = BN_FIN_CH channels (threadIdx.x: adjacent threads
+// read adjacent channels of one slab row) x BN_FIN_TY slab rows; grid =
+// (channel chunks, Y slab chunks), so the block count follows the slab
+// bytes, not C. Every sum runs in an order fixed by indices:
+//   1. thread (tx, ty) adds rows r0+ty, r0+ty+TY, ... of its chunk in
+//      double, the TY partials combine in LDS in ty order;
+//   2. Y > 1: the block stores its double partial to part[chunk][y][2][CH]
+//      and draws a ticket on its channel chunk (stores, vmcnt(0) in
+//      every wave, barrier, agent-scope release, wait, relaxed agent
+//      fetch_add). The block that draws the last ticket acquires, sums
+//      the Y partials the same way (y = ty, ty+TY, ... then ty order),
+//      resets the ticket and writes the results. No block waits on
+//      another; the ticket words live in a zero-initialised workspace.
+#define BN_FIN_CH 32
+#define BN_FIN_TY 8
+#define BN_FIN_ROWS 32   // slab rows per block (before the Y cap)
+#define BN_FIN_YMAX 64   // Y * 2 * CH doubles = 32 KB per channel chunk
+
+struct BnFinParams {
+  const void* sums;      // [S][2][C] of ST
+  double* part;          // [cchunks][Y][2][BN_FIN_CH]
+  unsigned* tickets;     // [cchunks], zero between launches
+  int64_t C, S;
+  int rows_per;          // slab rows per block
+  double count;
+  // forward
+  float* mean; float* invstd; float* running_mean; float* running_var;
+  float eps, momentum;
+  // backward
+  const float* gamma; const float* invstd_in;
+  float* dgamma; float* dbeta; float* k;  // k = [3][C]
+  int training;
+};
+
+template <typename ST, bool BWD>
+__global__ __launch_bounds__(BN_FIN_CH * BN_FIN_TY)
+void bn_finalize_kernel(BnFinParams q) {
+  __shared__ double sh[2][BN_FIN_TY][BN_FIN_CH];
+  __shared__ int is_last;
+  const int tx = threadIdx.x, ty = threadIdx.y;
+  const int t = ty * BN_FIN_CH + tx;
+  const int Y = gridDim.y;
+  const int64_t c = (int64_t)blockIdx.x * BN_FIN_CH + tx;
+  const ST* sums = static_cast<const ST*>(q.sums);
+
+  // level 1: this block's slab rows
+  double a0 = 0.0, a1 = 0.0;
+  if (c < q.C) {
+    const int64_t r0 = (int64_t)blockIdx.y * q.rows_per;
+    const int64_t r1 = i64min(r0 + q.rows_per, q.S);
+    int64_t r = r0 + ty;
+    for (; r + 3 * BN_FIN_TY < r1; r += 4 * BN_FIN_TY) {
+      ST v0[4], v1[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        v0[j] = sums[((r + j * BN_FIN_TY) * 2 + 0) * q.C + c];
+        v1[j] = sums[((r + j * BN_FIN_TY) * 2 + 1) * q.C + c];
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        a0 += (double)v0[j];
+        a1 += (double)v1[j];
+      }
+    }
+    for (; r < r1; r += BN_FIN_TY) {
+      a0 += (double)sums[(r * 2 + 0) * q.C + c];
+      a1 += (double)sums[(r * 2 + 1) * q.C + c];
+    }
   }
-  auto op = [](double v) { return wave_reduce_sum(v); };
-  s = block_reduce(s, tmp, op, 0.0);
+  sh[0][ty][tx] = a0;
+  sh[1][ty][tx] = a1;
   __syncthreads();
-  ss = block_reduce(ss, tmp, op, 0.0);
-  if (threadIdx.x != 0) return;
-  const double m = s / count;
-  double var = ss / count - m * m;
-  var = var < 0.0 ? 0.0 : var;
-  mean[c] = (float)m;
-  invstd[c] = (float)rsqrt(var + (double)eps);
-  if (running_mean != nullptr) {
-    const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-    running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)m;
-    running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
+  // threads 0..2*CH-1: (which, channel) = (t / CH, t % CH)
+  double v = 0.0;
+  if (t < 2 * BN_FIN_CH) {
+#pragma unroll
+    for (int j = 0; j < BN_FIN_TY; ++j) v += sh[ty][j][tx];
+  }
+
+  if (Y > 1) {
+    double* part = q.part + (int64_t)blockIdx.x * Y * 2 * BN_FIN_CH;
+    if (t < 2 * BN_FIN_CH) part[(int64_t)blockIdx.y * 2 * BN_FIN_CH + t] = v;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (t == 0) {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      const unsigned ticket = __hip_atomic_fetch_add(
+          &q.tickets[blockIdx.x], 1u, __ATOMIC_RELAXED,
+          __HIP_MEMORY_SCOPE_AGENT);
+      const int last = ticket == (unsigned)(Y - 1);
+      if (last) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        // every arrival is in: the next launch finds the word at zero
+        __hip_atomic_store(&q.tickets[blockIdx.x], 0u, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+      }
+      is_last = last;
+    }
+    __syncthreads();
+    if (!is_last) return;
+    // level 2: the Y partials of this channel chunk, in index order
+    a0 = 0.0;
+    a1 = 0.0;
+    for (int y = ty; y < Y; y += BN_FIN_TY) {
+      a0 += part[(int64_t)(y * 2 + 0) * BN_FIN_CH + tx];
+      a1 += part[(int64_t)(y * 2 + 1) * BN_FIN_CH + tx];
+    }
+    sh[0][ty][tx] = a0;
+    sh[1][ty][tx] = a1;
+    __syncthreads();
+    v = 0.0;
+    if (t < 2 * BN_FIN_CH) {
+#pragma unroll
+      for (int j = 0; j < BN_FIN_TY; ++j) v += sh[ty][j][tx];
+    }
+  }
+
+  // hand the second sum over to the thread that owns the channel
+  __syncthreads();
+  if (t < 2 * BN_FIN_CH) sh[ty][0][tx] = v;
+  __syncthreads();
+  if (t >= BN_FIN_CH || c >= q.C) return;
+  const double s0 = sh[0][0][tx], s1 = sh[1][0][tx];
+  if (!BWD) {
+    // s0 = sum x, s1 = sum x^2
+    const double m = s0 / q.count;
+    double var = s1 / q.count - m * m;
+    var = var < 0.0 ? 0.0 : var;
+    q.mean[c] = (float)m;
+    q.invstd[c] = (float)rsqrt(var + (double)q.eps);
+    if (q.running_mean != nullptr) {
+      const double unbiased =
+          q.count > 1.0 ? var * q.count / (q.count - 1.0) : var;
+      q.running_mean[c] = (1.f - q.momentum) * q.running_mean[c] +
+                          q.momentum * (float)m;
+      q.running_var[c] = (1.f - q.momentum) * q.running_var[c] +
+                         q.momentum * (float)unbiased;
+    }
+  } else {
+    // s0 = sum dy', s1 = sum dy' * xhat
+    q.dgamma[c] = (float)s1;
+    q.dbeta[c] = (float)s0;
+    q.k[c] = q.gamma[c] * q.invstd_in[c];                        // k1
+    q.k[q.C + c] = q.training ? (float)(s0 / q.count) : 0.f;     // k2
+    q.k[2 * q.C + c] = q.training ? (float)(s1 / q.count) : 0.f; // k3
   }
 }
 
@@ -629,7 +749,7 @@ template <typename T, int ACT, bool MASKED = false>
 __global__ void bn_bwd_reduce_nhwc_vec_kernel(
     const T* __restrict__ dy, const T* __restrict__ y,
     const T* __restrict__ x, const float* __restrict__ mean,
-    const float* __restrict__ invstd, double* __restrict__ sums,
+    const float* __restrict__ invstd, float* __restrict__ sums,
     const unsigned char* __restrict__ msk,
     int64_t rows, int64_t C, int CG8) {
   typedef __attribute__((ext_vector_type(8))) short short8x;
@@ -700,37 +820,10 @@ __global__ void bn_bwd_reduce_nhwc_vec_kernel(
       }
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      sums[((int64_t)blockIdx.y * 2 + 0) * C + c0 + j] = (double)sdy[j];
-      sums[((int64_t)blockIdx.y * 2 + 1) * C + c0 + j] = (double)sdyx[j];
+      sums[((int64_t)blockIdx.y * 2 + 0) * C + c0 + j] = sdy[j];
+      sums[((int64_t)blockIdx.y * 2 + 1) * C + c0 + j] = sdyx[j];
     }
   }
-}
-
-__global__ void bn_bwd_finalize_kernel(const double* __restrict__ sums,
-                                       const float* __restrict__ gamma,
-                                       const float* __restrict__ invstd,
-                                       float* __restrict__ dgamma,
-                                       float* __restrict__ dbeta,
-                                       float* __restrict__ k,  // [3][C]
-                                       int64_t C, int64_t S, double count,
-                                       int training) {
-  __shared__ double tmp[16];
-  const int64_t c = blockIdx.x;
-  double sdy = 0.0, sdyx = 0.0;
-  for (int64_t b = threadIdx.x; b < S; b += blockDim.x) {
-    sdy += sums[(b * 2 + 0) * C + c];
-    sdyx += sums[(b * 2 + 1) * C + c];
-  }
-  auto op = [](double v) { return wave_reduce_sum(v); };
-  sdy = block_reduce(sdy, tmp, op, 0.0);
-  __syncthreads();
-  sdyx = block_reduce(sdyx, tmp, op, 0.0);
-  if (threadIdx.x != 0) return;
-  dgamma[c] = (float)sdyx;
-  dbeta[c] = (float)sdy;
-  k[c] = gamma[c] * invstd[c];                       // k1
-  k[C + c] = training ? (float)(sdy / count) : 0.f;  // k2 (mean of dy')
-  k[2 * C + c] = training ? (float)(sdyx / count) : 0.f;  // k3
 }
 
 // dx = k1 * (dy' - k2 - xhat*k3); optionally dres = dy'
@@ -762,7 +855,8 @@ static inline int elementwise_grid(int64_t total, int block) {
 
 
 // Reduction-kernel dispatch geometry, shared by the launchers AND the
-// workspace sizing in the bindings (partial slab = [S][2][C] doubles).
+// workspace sizing in the bindings through bn_workspace_plan (partial
+// slab = [S][2][C], fp32 from the bf16 vec kernels, else double).
 // g_bn_variant: 0 = shape-adaptive (vec reductions for C <= 512 where
 // the probe shows them ahead), 1 = scalar, 2 = vec.
 struct BnGeom { bool vec; int64_t cblocks, S; };
@@ -795,8 +889,50 @@ int64_t ddlb::bn_reduce_gridS(int64_t N, int64_t C, int64_t HW, int nhwc,
   return i64max(S, 1);
 }
 
+// fp32 slabs exactly where the bf16 vec reduce kernels run
+static bool bn_slab_f32(int64_t rows, int64_t C, int nhwc, int elsize) {
+  return nhwc && elsize == 2 && bn_reduce_geom(rows, C, elsize).vec;
+}
+
+// finalize grid along the slabs: BN_FIN_ROWS rows per block, at most
+// BN_FIN_YMAX blocks per channel chunk
+static int64_t bn_fin_Y(int64_t S) {
+  return i64min((S + BN_FIN_ROWS - 1) / BN_FIN_ROWS, BN_FIN_YMAX);
+}
+
+ddlb::BnWorkspacePlan ddlb::bn_workspace_plan(int64_t N, int64_t C,
+                                              int64_t HW, int nhwc,
+                                              int elsize) {
+  BnWorkspacePlan p;
+  p.S = bn_reduce_gridS(N, C, HW, nhwc, elsize);
+  p.slab_f32 = bn_slab_f32(N * HW, C, nhwc, elsize) ? 1 : 0;
+  p.slab_bytes = p.S * 2 * C * (p.slab_f32 ? 4 : 8);
+  p.cchunks = (C + BN_FIN_CH - 1) / BN_FIN_CH;
+  p.Y = bn_fin_Y(p.S);
+  p.part_doubles = p.Y > 1 ? p.cchunks * p.Y * 2 * BN_FIN_CH : 0;
+  return p;
+}
+
+// one launch for either direction; q carries the direction's pointers
+template <bool BWD>
+static void bn_finalize_launch(BnFinParams q, bool slab_f32,
+                               hipStream_t stream) {
+  const int64_t Y = bn_fin_Y(q.S);
+  q.rows_per = (int)((q.S + Y - 1) / Y);
+  const dim3 grid((unsigned)((q.C + BN_FIN_CH - 1) / BN_FIN_CH),
+                  (unsigned)Y);
+  const dim3 block(BN_FIN_CH, BN_FIN_TY);
+  if (slab_f32)
+    hipLaunchKernelGGL((bn_finalize_kernel<float, BWD>), grid, block, 0,
+                       stream, q);
+  else
+    hipLaunchKernelGGL((bn_finalize_kernel<double, BWD>), grid, block, 0,
+                       stream, q);
+  HIP_CHECK_LAST();
+}
+
 template <typename T>
-void ddlb::launch_bn_stats(const T* x, double* sums, int64_t N, int64_t C,
+void ddlb::launch_bn_stats(const T* x, void* sums, int64_t N, int64_t C,
                            int64_t HW, int64_t S, int nhwc,
                            hipStream_t stream) {
   const int block = 256;
@@ -807,33 +943,38 @@ void ddlb::launch_bn_stats(const T* x, double* sums, int64_t N, int64_t C,
       const int CG8 = (int)i64min(C / 8, 64);
       hipLaunchKernelGGL((bn_stats_nhwc_vec_kernel<T>),
                          dim3(g.cblocks, S),
-                         dim3(block), 0, stream, x, sums, rows, C, CG8);
+                         dim3(block), 0, stream, x, (float*)sums, rows, C,
+                         CG8);
     } else if (g.vec && sizeof(T) == 4) {
       const int CG4 = (int)i64min(C / 4, 64);
       hipLaunchKernelGGL(bn_stats_nhwc_vec_f32_kernel, dim3(g.cblocks, S),
-                         dim3(block), 0, stream, (const float*)x, sums,
-                         rows, C, CG4);
+                         dim3(block), 0, stream, (const float*)x,
+                         (double*)sums, rows, C, CG4);
     } else {
       const int CG = C >= 64 ? 64 : (int)C;
       hipLaunchKernelGGL((bn_stats_nhwc_kernel<T>), dim3(g.cblocks, S),
-                         dim3(block), 0, stream, x, sums, rows, C, CG);
+                         dim3(block), 0, stream, x, (double*)sums, rows, C,
+                         CG);
     }
   } else {
     hipLaunchKernelGGL((bn_stats_kernel<T>), dim3(C, S), dim3(block), 0,
-                       stream, x, sums, N, C, HW);
+                       stream, x, (double*)sums, N, C, HW);
   }
   HIP_CHECK_LAST();
 }
 
-void ddlb::launch_bn_finalize(double* sums, float* mean, float* invstd,
+void ddlb::launch_bn_finalize(const void* sums, int slab_f32, double* part,
+                              unsigned* tickets, float* mean, float* invstd,
                               float* rm, float* rv, int64_t C, int64_t S,
                               double count, float eps, float momentum,
                               hipStream_t stream) {
-  const int block = 1024;
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3((unsigned)C),
-                     dim3(block), 0, stream, sums, mean, invstd, rm, rv, C,
-                     S, count, eps, momentum);
-  HIP_CHECK_LAST();
+  BnFinParams q = {};
+  q.sums = sums; q.part = part; q.tickets = tickets;
+  q.C = C; q.S = S; q.count = count;
+  q.mean = mean; q.invstd = invstd;
+  q.running_mean = rm; q.running_var = rv;
+  q.eps = eps; q.momentum = momentum;
+  bn_finalize_launch<false>(q, slab_f32 != 0, stream);
 }
 
 template <typename T>
@@ -909,7 +1050,7 @@ bool ddlb::launch_bn_apply(const T* x, const T* res, T* y, const float* mean,
 template <typename T>
 void ddlb::launch_bn_bwd_reduce(const T* dy, const T* y, const T* x,
                                 const float* mean, const float* invstd,
-                                double* sums, const unsigned char* msk,
+                                void* sums_v, const unsigned char* msk,
                                 int64_t N, int64_t C, int64_t HW, int64_t S,
                                 int act, int nhwc, hipStream_t stream) {
   const int block = 256;
@@ -922,7 +1063,8 @@ void ddlb::launch_bn_bwd_reduce(const T* dy, const T* y, const T* x,
 #define CASE(ACT, MSK)                                                      \
       hipLaunchKernelGGL((bn_bwd_reduce_nhwc_vec_kernel<T, ACT, MSK>),      \
                          dim3(g.cblocks, S), dim3(block), 0, stream, dy,    \
-                         y, x, mean, invstd, sums, msk, rows, C, CG8)
+                         y, x, mean, invstd, (float*)sums_v, msk, rows, C,  \
+                         CG8)
       if (act == 0) CASE(0, false);
       else if (act == 1) { if (masked) CASE(1, true); else CASE(1, false); }
       else { if (masked) CASE(2, true); else CASE(2, false); }
@@ -932,7 +1074,8 @@ void ddlb::launch_bn_bwd_reduce(const T* dy, const T* y, const T* x,
 #define CASE(ACT, MSK)                                                      \
       hipLaunchKernelGGL((bn_bwd_reduce_nhwc_kernel<T, ACT, MSK>),          \
                          dim3(g.cblocks, S), dim3(block), 0, stream, dy,    \
-                         y, x, mean, invstd, sums, msk, rows, C, CG)
+                         y, x, mean, invstd, (double*)sums_v, msk, rows, C, \
+                         CG)
       if (act == 0) CASE(0, false);
       else if (act == 1) { if (masked) CASE(1, true); else CASE(1, false); }
       else { if (masked) CASE(2, true); else CASE(2, false); }
@@ -942,7 +1085,7 @@ void ddlb::launch_bn_bwd_reduce(const T* dy, const T* y, const T* x,
 #define CASE(ACT)                                                          \
     hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, ACT>), dim3(C, S),         \
                        dim3(block), 0, stream, dy, y, x, mean, invstd,     \
-                       sums, N, C, HW)
+                       (double*)sums_v, N, C, HW)
     if (act == 0) CASE(0);
     else if (act == 1) CASE(1);
     else CASE(2);
@@ -951,16 +1094,19 @@ void ddlb::launch_bn_bwd_reduce(const T* dy, const T* y, const T* x,
   HIP_CHECK_LAST();
 }
 
-void ddlb::launch_bn_bwd_finalize(double* sums, const float* gamma,
-                                  const float* invstd, float* dgamma,
-                                  float* dbeta, float* k, int64_t C, int64_t S,
-                                  double count, int training,
-                                  hipStream_t stream) {
-  const int block = 1024;
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)C),
-                     dim3(block), 0, stream, sums, gamma, invstd, dgamma,
-                     dbeta, k, C, S, count, training);
-  HIP_CHECK_LAST();
+void ddlb::launch_bn_bwd_finalize(const void* sums, int slab_f32,
+                                  double* part, unsigned* tickets,
+                                  const float* gamma, const float* invstd,
+                                  float* dgamma, float* dbeta, float* k,
+                                  int64_t C, int64_t S, double count,
+                                  int training, hipStream_t stream) {
+  BnFinParams q = {};
+  q.sums = sums; q.part = part; q.tickets = tickets;
+  q.C = C; q.S = S; q.count = count;
+  q.gamma = gamma; q.invstd_in = invstd;
+  q.dgamma = dgamma; q.dbeta = dbeta; q.k = k;
+  q.training = training;
+  bn_finalize_launch<true>(q, slab_f32 != 0, stream);
 }
 
 template <typename T>
@@ -1042,14 +1188,14 @@ void ddlb::launch_bn_bwd_dx(const T* dy, const T* y, const T* x,
 
 #define INSTANTIATE(T)                                                        \
   template void ddlb::launch_bn_stats<T>(                                     \
-      const T*, double*, int64_t, int64_t, int64_t, int64_t, int,             \
+      const T*, void*, int64_t, int64_t, int64_t, int64_t, int,             \
       hipStream_t);                                                           \
   template bool ddlb::launch_bn_apply<T>(                                     \
       const T*, const T*, T*, const float*, const float*, const float*,       \
       const float*, unsigned char*, int64_t, int64_t, int64_t, int, int,      \
       hipStream_t);                                                           \
   template void ddlb::launch_bn_bwd_reduce<T>(                                \
-      const T*, const T*, const T*, const float*, const float*, double*,      \
+      const T*, const T*, const T*, const float*, const float*, void*,        \
       const unsigned char*, int64_t, int64_t, int64_t, int64_t, int, int,     \
       hipStream_t);                                                           \
   template void ddlb::launch_bn_bwd_dx<T>(                                    \

@@ -25,6 +25,10 @@
 //   * split-P partial slabs [split][K][RSC] fp32 + a combine kernel —
 //     no per-tile global atomics (a C64K64R1 layer would serialize
 //     ~2048 atomic adds per dw element).
+//   * bf16 output (the weight's dtype, same (K, R*S*C) memory): the
+//     epilogue rounds the accumulator when split == 1, otherwise an
+//     ordered combine adds each element's slabs in slab order and rounds
+//     once — no memset, no atomics, the same bits every call.
 //
 // Constraints: bf16, K % 8 == 0, C % 8 == 0.
 
@@ -43,6 +47,7 @@ struct WgradParams {
   const bf16* x;      // (N,H,W,C) memory
   const bf16* dy;     // (N,OH,OW,K) memory
   float* dw;          // (K, R*S*C) fp32 output
+  bf16* dwb;          // non-null: bf16 output instead of dw
   float* part;        // [split][K][RSC] fp32 partial slabs (split>1)
   const bf16* zero;
   int N, H, W, C, K, OH, OW, R, S, stride, pad;
@@ -285,10 +290,62 @@ void conv_wgrad2_kernel(WgradParams q) {
 #pragma unroll
       for (int nf = 0; nf < NFS; ++nf) {
         const long rsc = rb + (wc * NFS + nf) * 16 + (lane & 15);
-        if (rsc < q.RSC) out[k * q.RSC + rsc] = acc[mf][nf][reg];
+        if (rsc >= q.RSC) continue;
+        if (q.split_p == 1 && q.dwb != nullptr)
+          q.dwb[k * q.RSC + rsc] = __float2bfloat16(acc[mf][nf][reg]);
+        else
+          out[k * q.RSC + rsc] = acc[mf][nf][reg];
       }
     }
   }
+}
+
+// Ordered combine: element i's slabs are added in slab order. Thread
+// (tx, ty) owns V consecutive elements and slabs [64*ty, 64*ty + 64),
+// summed from 0.f upwards exactly as wgrad_combine_kernel sums a 64-slab
+// chunk; blockDim.y > 1 (split > 64) then adds the chunk sums in ty
+// order through LDS, so a small dw with many slabs still spreads over
+// blockDim.y times the threads. The result is rounded once to OutT.
+template <typename OutT, int V, int TX, int TY>
+__global__ void wgrad_combine_ordered_kernel(const float* __restrict__ part,
+                                             OutT* __restrict__ dw,
+                                             long total, long stride_elems,
+                                             int split) {
+  __shared__ float sh[TY][TX][V];
+  const int tx = threadIdx.x, ty = threadIdx.y;
+  const long i = ((long)blockIdx.x * TX + tx) * V;
+  const int ps0 = ty * 64;
+  const int ps1 = min(ps0 + 64, split);
+  float s[V];
+#pragma unroll
+  for (int j = 0; j < V; ++j) s[j] = 0.f;
+  if (i < total) {
+#pragma unroll 4
+    for (int ps = ps0; ps < ps1; ++ps) {
+      const float* src = part + ps * stride_elems + i;
+      if constexpr (V == 4) {
+        typedef __attribute__((ext_vector_type(4))) float float4x;
+        const float4x v = *reinterpret_cast<const float4x*>(src);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s[j] += v[j];
+      } else {
+#pragma unroll
+        for (int j = 0; j < V; ++j) s[j] += src[j];
+      }
+    }
+  }
+  if (TY > 1 && blockDim.y > 1) {
+#pragma unroll
+    for (int j = 0; j < V; ++j) sh[ty][tx][j] = s[j];
+    __syncthreads();
+    if (ty != 0) return;
+    for (int g = 1; g < (int)blockDim.y; ++g)
+#pragma unroll
+      for (int j = 0; j < V; ++j) s[j] += sh[g][tx][j];
+  }
+  if (i >= total) return;
+#pragma unroll
+  for (int j = 0; j < V; ++j) dw[i + j] = from_f32<OutT>(s[j]);
 }
 
 // 2D combine: blockIdx.y covers 64-slab chunks (atomics per element are
@@ -362,11 +419,12 @@ void ddlb::launch_conv_wgrad(const void* x, const void* dy, float* dw,
                              float* part_ws, long part_cap, const void* zero,
                              int N, int H, int W, int C, int K, int OH, int OW,
                              int R, int S, int stride, int pad,
-                             hipStream_t stream) {
+                             hipStream_t stream, void* dw_bf16) {
   WgradParams q;
   q.x = (const bf16*)x;
   q.dy = (const bf16*)dy;
   q.dw = dw;
+  q.dwb = (bf16*)dw_bf16;
   q.part = part_ws;
   q.zero = (const bf16*)zero;
   q.N = N; q.H = H; q.W = W; q.C = C; q.K = K; q.OH = OH; q.OW = OW;
@@ -388,7 +446,23 @@ void ddlb::launch_conv_wgrad(const void* x, const void* dy, float* dw,
     wg_launch<128, 64, 4, 1, 256, false>(q, r1, grid, lds, stream);
   else
     wg_launch<64, 64, 1, 4, 256, false>(q, r1, grid, lds, stream);
-  if (q.split_p > 1) {
+  if (q.split_p > 1 && q.dwb != nullptr) {
+    // total % 8 == 0 (C % 8 == 0); psb <= 4 (split <= 256)
+    const long total = q.K * q.RSC;
+    if (pl.psb > 4)
+      throw std::runtime_error("conv_wgrad: ordered combine needs split <= 256");
+    if (pl.psb <= 1) {
+      const unsigned blocks = (unsigned)((total / 4 + 255) / 256);
+      hipLaunchKernelGGL((wgrad_combine_ordered_kernel<bf16, 4, 256, 1>),
+                         dim3(blocks), dim3(256, 1), 0, stream, part_ws,
+                         q.dwb, total, total, q.split_p);
+    } else {
+      const unsigned blocks = (unsigned)((total + 31) / 32);
+      hipLaunchKernelGGL((wgrad_combine_ordered_kernel<bf16, 1, 32, 4>),
+                         dim3(blocks), dim3(32, (unsigned)pl.psb), 0, stream,
+                         part_ws, q.dwb, total, total, q.split_p);
+    }
+  } else if (q.split_p > 1) {
     const long total = q.K * q.RSC;
     const int blocks = (int)i64min((total + 255) / 256, 2048);
     const int psb = (int)pl.psb;

@@ -26,10 +26,28 @@ void launch_fused_adam(uintptr_t* params, uintptr_t* grads, uintptr_t* ms,
 void set_bn_variant(int v);
 int64_t bn_reduce_gridS(int64_t N, int64_t C, int64_t HW, int nhwc,
                         int elsize);
+// Workspace of one BN reduce + finalize pair, from the same geometry
+// decision the launchers take: the reduce kernels write [S][2][C] partial
+// slabs (fp32 from the bf16 vec kernels, whose partials are fp32; double
+// from the scalar and fp32 kernels); the finalize grid is (cchunks, Y)
+// and, when Y > 1, hands double partials through part[part_doubles] and
+// one ticket word per channel chunk (zero before the first launch; the
+// kernel leaves them zero).
+struct BnWorkspacePlan {
+  int64_t S;
+  int slab_f32;
+  int64_t slab_bytes;
+  int64_t cchunks, Y;
+  int64_t part_doubles;
+};
+BnWorkspacePlan bn_workspace_plan(int64_t N, int64_t C, int64_t HW, int nhwc,
+                                  int elsize);
+// sums: the slab workspace (void*: its element type follows the plan)
 template <typename T>
-void launch_bn_stats(const T*, double*, int64_t, int64_t, int64_t, int64_t,
-                     int, hipStream_t);
-void launch_bn_finalize(double*, float*, float*, float*, float*,
+void launch_bn_stats(const T*, void* sums, int64_t, int64_t, int64_t,
+                     int64_t, int, hipStream_t);
+void launch_bn_finalize(const void* sums, int slab_f32, double* part,
+                        unsigned* tickets, float*, float*, float*, float*,
                         int64_t, int64_t, double, float, float,
                         hipStream_t);
 template <typename T>
@@ -38,10 +56,11 @@ bool launch_bn_apply(const T*, const T*, T*, const float*, const float*,
                      int64_t, int64_t, int, int, hipStream_t);
 template <typename T>
 void launch_bn_bwd_reduce(const T*, const T*, const T*, const float*,
-                          const float*, double*, const unsigned char*,
+                          const float*, void* sums, const unsigned char*,
                           int64_t, int64_t, int64_t, int64_t,
                           int, int, hipStream_t);
-void launch_bn_bwd_finalize(double*, const float*, const float*,
+void launch_bn_bwd_finalize(const void* sums, int slab_f32, double* part,
+                            unsigned* tickets, const float*, const float*,
                             float*, float*, float*, int64_t, int64_t,
                             double, int, hipStream_t);
 template <typename T>
@@ -106,11 +125,24 @@ struct ConvWgradPlan {
 };
 ConvWgradPlan conv_wgrad_plan(int N, int C, int K, int OH, int OW, int R,
                               int S, int stride, int pad, long part_cap);
+// dw_bf16 == nullptr: fp32 dw in (K, R*S*C) memory. Otherwise dw is
+// unused and the result goes to dw_bf16 in the same layout, each element
+// the round-to-nearest-even bf16 of its fp32 sum: from the kernel's
+// epilogue (split == 1) or from a combine that adds every element's
+// slabs in slab order (no memset, no atomics).
 void launch_conv_wgrad(const void* x, const void* dy, float* dw,
                        float* part_ws, long part_cap, const void* zero,
                        int N, int H, int W, int C, int K, int OH, int OW,
                        int R, int S, int stride, int pad,
-                       hipStream_t stream);
+                       hipStream_t stream, void* dw_bf16 = nullptr);
+
+// ---- conv_weight_layout.hip: bf16 batched transpose -------------------
+// in[b][m][n] (row stride in_rs, batch stride in_bs) ->
+// out[b][n][m] (row stride out_rs, batch stride out_bs); M % 8 == 0,
+// Nn % 8 == 0, every stride a multiple of 8 elements.
+void launch_weight_transpose(const void* in, void* out, long B, long M,
+                             long Nn, long in_rs, long in_bs, long out_rs,
+                             long out_bs, hipStream_t stream);
 
 // ---- conv_stem.hip ----------------------------------------------------
 void launch_conv_stem_fwd(const void* x, const void* w, void* y, int N,

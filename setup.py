@@ -28,6 +28,7 @@ KERNEL_SOURCES = [
     "conv_mfma.hip",
     "conv_mfma2.hip",
     "conv_stem.hip",
+    "conv_weight_layout.hip",
     "conv_wgrad.hip",
     "cross_entropy.hip",
     "depthwise_conv.hip",
