@@ -1,10 +1,15 @@
 #!/usr/bin/env python3
-"""Within-process A/B probe of the BN kernel variants.
+"""Per-phase timing of the fused BN+act kernels on the ResNet-50 shapes.
 
 Times the raw bindings per phase (stats+apply = train fwd; apply only =
-eval fwd; reduce+finalize+dx = bwd) for each variant interleaved in one
-process (cdna_hip_programming.md §5.4 rule 24)."""
+eval fwd; reduce+finalize+dx = bwd, from y and from the 1-bit mask) on the
+path the dispatch plan selects, and prints the plan's kernel kinds next to
+the numbers. To re-tune a threshold, edit its named constant in
+bn_act.hip and compare this probe's output against the previous build's
+(same process order, cdna_hip_programming.md §5.4 rule 24); --repeats
+gives the probe's own repeat-to-repeat spread."""
 
+import argparse
 import json
 import os
 import sys
@@ -31,6 +36,9 @@ def t_ms(fn, iters=15, warmup=4):
 
 
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=1)
+    args = ap.parse_args()
     from ddlbench_amd.ops import require_extension
     ext = require_extension()
     dev = torch.device("cuda", 0)
@@ -50,8 +58,12 @@ def main():
         mask = outs[3] if len(outs) > 3 else None
         nb = N * C * H * W * 2 / 1e9
         row = {"shape": f"{N}x{C}x{H}x{W}"}
-        for variant in (1, 2):
-            ext.set_bn_variant(variant)
+        pl = ext.bn_plan(N, C, H * W, True, 2, 1, True, mask is not None)
+        ev = ext.bn_plan(N, C, H * W, True, 2, 1, False, False)
+        row.update(reduce=pl["reduce"], S=pl["S"], slab=pl["slab"],
+                   apply=pl["apply"], apply_eval=ev["apply"],
+                   dx_mask=pl["dx"], dx_y=ev["dx"])
+        for rep in range(args.repeats):
             tf = t_ms(lambda: ext.bn_act_fwd(x, res, g, b, rm, rv, True,
                                              0.1, 1e-5, 1, True))
             te = t_ms(lambda: ext.bn_act_fwd(x, res, g, b, rm, rv, False,
@@ -62,16 +74,14 @@ def main():
                                                g, 1, True, True, True,
                                                mask))
                    if mask is not None else float("nan"))
-            row[f"v{variant}_fwd_ms"] = round(tf, 3)
-            row[f"v{variant}_fwd_TBs"] = round(4 * nb / tf, 2)
-            row[f"v{variant}_apply_ms"] = round(te, 3)
-            row[f"v{variant}_apply_TBs"] = round(3 * nb / te, 2)
-            row[f"v{variant}_stats_TBs"] = round(nb / max(tf - te, 1e-5), 2)
-            row[f"v{variant}_bwd_ms"] = round(tb, 3)
-            row[f"v{variant}_bwd_TBs"] = round(8 * nb / tb, 2)
-            row[f"v{variant}_bwdmask_ms"] = round(tbm, 3)
-        ext.set_bn_variant(0)
-        print(json.dumps(row), flush=True)
+            row.update(rep=rep, fwd_ms=round(tf, 3),
+                       fwd_TBs=round(4 * nb / tf, 2),
+                       apply_ms=round(te, 3),
+                       apply_TBs=round(3 * nb / te, 2),
+                       stats_TBs=round(nb / max(tf - te, 1e-5), 2),
+                       bwd_ms=round(tb, 3), bwd_TBs=round(8 * nb / tb, 2),
+                       bwdmask_ms=round(tbm, 3))
+            print(json.dumps(row), flush=True)
 
 
 if __name__ == "__main__":

@@ -70,8 +70,8 @@ torch::Tensor zero_page(const torch::Tensor& like) {
   return cached_ws(zp, like, at::kBFloat16, 16, 0, /*zeroed=*/true);
 }
 
-// BN reduce + finalize workspaces, sized by bn_workspace_plan (the
-// launchers' own geometry decision).
+// BN reduce + finalize workspaces, sized by the bn_plan the launchers
+// walk.
 // sums: [S][2][C] partial slabs, fp32 or double by plan. Reduce-style
 // kernels write plain per-block stores and the finalize kernel sums over
 // S — no cross-block atomics (a C=64 layer at S~1500 slices serialized
@@ -81,21 +81,35 @@ torch::Tensor zero_page(const torch::Tensor& like) {
 // per-channel-chunk ticket words. The tickets are zeroed once, at
 // allocation; each launch leaves them at zero.
 struct BnWorkspace {
-  BnWorkspacePlan plan;
   torch::Tensor sums, part, tickets;
 };
-BnWorkspace bn_workspace(const torch::Tensor& x, int64_t N, int64_t C,
-                         int64_t HW, bool nhwc) {
+BnWorkspace bn_workspace(const torch::Tensor& x, const BnPlan& plan) {
   static WsCache ws_sums, ws_part, ws_tickets;
   BnWorkspace w;
-  w.plan = bn_workspace_plan(N, C, HW, nhwc, (int)x.element_size());
-  w.sums = cached_ws(ws_sums, x, at::kDouble, (w.plan.slab_bytes + 7) / 8,
+  w.sums = cached_ws(ws_sums, x, at::kDouble, (plan.slab_bytes + 7) / 8,
                      1 << 18);
   w.part = cached_ws(ws_part, x, at::kDouble,
-                     std::max<int64_t>(w.plan.part_doubles, 1), 1 << 16);
-  w.tickets = cached_ws(ws_tickets, x, at::kInt, w.plan.cchunks, 1 << 10,
+                     std::max<int64_t>(plan.part_doubles, 1), 1 << 16);
+  w.tickets = cached_ws(ws_tickets, x, at::kInt, plan.cchunks, 1 << 10,
                         /*zeroed=*/true);
   return w;
+}
+
+const char* bn_name(BnReduce k) {
+  return k == BnReduce::nchw ? "nchw"
+         : k == BnReduce::nhwc_scalar ? "nhwc_scalar" : "nhwc_vec";
+}
+const char* bn_name(BnElt k) {
+  return k == BnElt::fixed_channel ? "fixed_channel"
+         : k == BnElt::vec ? "vec" : "scalar";
+}
+const char* bn_name(BnGate g) {
+  return g == BnGate::none ? "none" : g == BnGate::y ? "y" : "mask";
+}
+
+bool bn_layout_ok(const torch::Tensor& t, bool nhwc) {
+  return nhwc ? t.is_contiguous(at::MemoryFormat::ChannelsLast)
+              : t.is_contiguous();
 }
 
 // is_cuda + bf16 + channels_last, the operand contract of the conv and
@@ -183,27 +197,26 @@ std::vector<torch::Tensor> bn_act_fwd(
     double eps, int64_t act, bool nhwc) {
   TORCH_CHECK(x.is_cuda(), "x must be on the HIP device");
   TORCH_CHECK(x.dim() == 4, "x must be 4-D");
-  TORCH_CHECK(nhwc ? x.is_contiguous(at::MemoryFormat::ChannelsLast)
-                   : x.is_contiguous(), "x layout mismatch");
+  TORCH_CHECK(bn_layout_ok(x, nhwc), "x layout mismatch");
   const int64_t N = x.size(0), C = x.size(1), HW = x.size(2) * x.size(3);
+  const BnPlan plan = bn_plan(N, C, HW, nhwc, (int)x.element_size(),
+                              (int)act, training, /*masked=*/0);
   auto s = cur_stream();
   auto fopt = x.options().dtype(at::kFloat);
   torch::Tensor mean = torch::empty({C}, fopt);
   torch::Tensor invstd = torch::empty({C}, fopt);
   if (training) {
-    const BnWorkspace ws = bn_workspace(x, N, C, HW, nhwc);
-    const int64_t S = ws.plan.S;
+    const BnWorkspace ws = bn_workspace(x, plan);
     dispatch_f32_bf16(x, [&](auto tag) {
       using T = decltype(tag);
-      launch_bn_stats<T>(dptr<T>(x), ws.sums.data_ptr(), N, C, HW, S, nhwc,
-                         s);
+      launch_bn_stats<T>(plan, dptr<T>(x), ws.sums.data_ptr(), s);
     });
     launch_bn_finalize(
-        ws.sums.data_ptr(), ws.plan.slab_f32, dptr<double>(ws.part),
+        plan, ws.sums.data_ptr(), dptr<double>(ws.part),
         dptr<unsigned>(ws.tickets), dptr<float>(mean), dptr<float>(invstd),
         running_mean ? dptr<float>(*running_mean) : nullptr,
-        running_var ? dptr<float>(*running_var) : nullptr, C, S,
-        (double)(N * HW), (float)eps, (float)momentum, s);
+        running_var ? dptr<float>(*running_var) : nullptr, (float)eps,
+        (float)momentum, s);
   } else {
     TORCH_CHECK(running_mean && running_var,
                 "eval mode needs running stats");
@@ -211,25 +224,20 @@ std::vector<torch::Tensor> bn_act_fwd(
     invstd.copy_((running_var->to(at::kFloat) + eps).rsqrt());
   }
   torch::Tensor y = torch::empty_like(x);
-  const int64_t total = x.numel();
   // 1-bit activation mask for the backward (bf16 NHWC training path):
   // bit (i & 7) of byte i/8 gates element i's activation gradient.
   torch::Tensor msk;
-  const bool want_mask =
-      training && act != 0 && nhwc && is_bf16(x) && C % 8 == 0;
-  if (want_mask)
-    msk = torch::empty({total / 8}, x.options().dtype(at::kByte));
-  // want_mask is bf16-only, so the fp32 launch never gets a mask pointer
-  const bool mask_written = dispatch_f32_bf16(x, [&](auto tag) {
+  if (plan.writes_mask)
+    msk = torch::empty({x.numel() / 8}, x.options().dtype(at::kByte));
+  dispatch_f32_bf16(x, [&](auto tag) {
     using T = decltype(tag);
-    return launch_bn_apply<T>(
-        dptr<T>(x), res ? dptr<T>(*res) : nullptr, dptr<T>(y),
+    launch_bn_apply<T>(
+        plan, dptr<T>(x), res ? dptr<T>(*res) : nullptr, dptr<T>(y),
         dptr<float>(mean), dptr<float>(invstd), dptr<float>(gamma),
         dptr<float>(beta),
-        want_mask ? msk.data_ptr<unsigned char>() : nullptr,
-        C, HW, total, (int)act, nhwc, s);
+        msk.defined() ? msk.data_ptr<unsigned char>() : nullptr, s);
   });
-  if (mask_written) return {y, mean, invstd, msk};
+  if (msk.defined()) return {y, mean, invstd, msk};
   return {y, mean, invstd};
 }
 
@@ -244,44 +252,74 @@ std::vector<torch::Tensor> bn_act_bwd(torch::Tensor dy,
   TORCH_CHECK(dy.is_cuda(), "dy must be on the HIP device");
   TORCH_CHECK(y_opt || msk,
               "bn_act_bwd needs y or the 1-bit activation mask");
+  TORCH_CHECK(dy.sizes() == x.sizes(), "dy and x differ in size");
+  TORCH_CHECK(dy.scalar_type() == x.scalar_type(),
+              "dy and x differ in dtype");
+  TORCH_CHECK(bn_layout_ok(dy, nhwc), "dy layout mismatch");
   const int64_t N = x.size(0), C = x.size(1), HW = x.size(2) * x.size(3);
+  TORCH_CHECK(!msk || msk->numel() == x.numel() / 8,
+              "the activation mask must hold numel/8 bytes");
+  // the fp32 kernels read y and never the mask
+  TORCH_CHECK(is_bf16(x) || y_opt, "fp32 backward needs y");
+  const BnPlan plan = bn_plan(N, C, HW, nhwc, (int)x.element_size(),
+                              (int)act, training,
+                              msk.has_value() && is_bf16(x));
+  TORCH_CHECK(y_opt || (plan.reduce_gate != BnGate::y &&
+                        plan.dx_gate != BnGate::y),
+              "bn_act_bwd: no masked kernel for this shape, y is needed");
   auto s = cur_stream();
   auto fopt = x.options().dtype(at::kFloat);
-  const BnWorkspace ws = bn_workspace(x, N, C, HW, nhwc);
-  const int64_t S = ws.plan.S;
+  const BnWorkspace ws = bn_workspace(x, plan);
   torch::Tensor dgamma = torch::empty({C}, fopt);
   torch::Tensor dbeta = torch::empty({C}, fopt);
   torch::Tensor k = torch::empty({3, C}, fopt);
   torch::Tensor dx = torch::empty_like(x);
   torch::Tensor dres =
       need_dres ? torch::empty_like(x) : torch::Tensor();
-  const int64_t total = x.numel();
   const unsigned char* mp =
-      msk ? msk->data_ptr<unsigned char>() : nullptr;
-  // the fp32 kernels read y and never the mask
-  if (!is_bf16(x)) {
-    TORCH_CHECK(y_opt, "fp32 backward needs y");
-    mp = nullptr;
-  }
+      msk && is_bf16(x) ? msk->data_ptr<unsigned char>() : nullptr;
   dispatch_f32_bf16(x, [&](auto tag) {
     using T = decltype(tag);
     const T* yp = y_opt ? dptr<T>(*y_opt) : nullptr;
-    launch_bn_bwd_reduce<T>(dptr<T>(dy), yp, dptr<T>(x), dptr<float>(mean),
-                            dptr<float>(invstd), ws.sums.data_ptr(), mp, N,
-                            C, HW, S, (int)act, nhwc, s);
-    launch_bn_bwd_finalize(ws.sums.data_ptr(), ws.plan.slab_f32,
-                           dptr<double>(ws.part), dptr<unsigned>(ws.tickets),
-                           dptr<float>(gamma),
+    launch_bn_bwd_reduce<T>(plan, dptr<T>(dy), yp, dptr<T>(x),
+                            dptr<float>(mean), dptr<float>(invstd),
+                            ws.sums.data_ptr(), mp, s);
+    launch_bn_bwd_finalize(plan, ws.sums.data_ptr(), dptr<double>(ws.part),
+                           dptr<unsigned>(ws.tickets), dptr<float>(gamma),
                            dptr<float>(invstd), dptr<float>(dgamma),
-                           dptr<float>(dbeta), dptr<float>(k), C, S,
-                           (double)(N * HW), training, s);
-    launch_bn_bwd_dx<T>(dptr<T>(dy), yp, dptr<T>(x), dptr<float>(mean),
+                           dptr<float>(dbeta), dptr<float>(k), training, s);
+    launch_bn_bwd_dx<T>(plan, dptr<T>(dy), yp, dptr<T>(x), dptr<float>(mean),
                         dptr<float>(invstd), dptr<float>(k), dptr<T>(dx),
-                        need_dres ? dptr<T>(dres) : nullptr, mp, C, HW,
-                        total, (int)act, nhwc, s);
+                        need_dres ? dptr<T>(dres) : nullptr, mp, s);
   });
   if (need_dres) return {dx, dgamma, dbeta, dres};
   return {dx, dgamma, dbeta};
+}
+
+py::dict bn_plan_py(int64_t N, int64_t C, int64_t HW, bool nhwc,
+                    int64_t elsize, int64_t act, bool training,
+                    bool masked) {
+  TORCH_CHECK(N >= 1 && C >= 1 && HW >= 1, "bn_plan: empty input");
+  TORCH_CHECK(elsize == 2 || elsize == 4, "bn_plan: elsize is 2 or 4");
+  const BnPlan p = bn_plan(N, C, HW, nhwc, (int)elsize, (int)act, training,
+                           masked);
+  py::dict d;
+  d["reduce"] = bn_name(p.reduce);
+  d["cblocks"] = p.reduce_grid.x;
+  d["S"] = p.reduce_grid.y;
+  d["slab"] = p.slab_f32 ? "f32" : "f64";
+  d["slab_bytes"] = p.slab_bytes;
+  d["reduce_gate"] = bn_name(p.reduce_gate);
+  d["cchunks"] = p.cchunks;
+  d["Y"] = p.Y;
+  d["part_doubles"] = p.part_doubles;
+  d["apply"] = bn_name(p.apply);
+  d["apply_grid"] = py::make_tuple(p.apply_grid.x, p.apply_grid.y);
+  d["writes_mask"] = p.writes_mask != 0;
+  d["dx"] = bn_name(p.dx);
+  d["dx_grid"] = py::make_tuple(p.dx_grid.x, p.dx_grid.y);
+  d["dx_gate"] = bn_name(p.dx_gate);
+  return d;
 }
 
 // ---- cross entropy ----------------------------------------------------
@@ -707,9 +745,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fused_sgd", &fused_sgd, "fused multi-tensor SGD step");
   m.def("fused_adam", &fused_adam, "fused multi-tensor Adam/AdamW step");
   m.def("bn_act_fwd", &bn_act_fwd, "fused BN+act(+res) forward");
-  m.def("set_bn_variant", &set_bn_variant,
-        "BN kernel variant for A/B probes (0 auto, 1 scalar-group, 2 vec)");
   m.def("bn_act_bwd", &bn_act_bwd, "fused BN+act(+res) backward");
+  m.def("bn_plan", &bn_plan_py,
+        "the dispatch plan the BN+act launchers walk (no device needed)",
+        py::arg("N"), py::arg("C"), py::arg("HW"), py::arg("nhwc"),
+        py::arg("elsize"), py::arg("act"), py::arg("training"),
+        py::arg("masked"));
   m.def("maxpool_fwd", &maxpool_fwd, "NHWC bf16 max-pool forward");
   m.def("maxpool_bwd", &maxpool_bwd, "NHWC bf16 max-pool backward");
   m.def("conv_igemm_fwd", &conv_igemm_fwd,

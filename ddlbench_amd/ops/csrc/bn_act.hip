@@ -1,4 +1,4 @@
-// Fused BatchNorm2d + activation (+ residual add) for gfx950, NCHW.
+// Fused BatchNorm2d + activation (+ residual add) for gfx950.
 //
 // Replaces the reference's unfused BatchNorm2d -> ReLU (-> add) chains
 // (SURVEY.md §2.6 "Key model ops") with single-pass kernels:
@@ -9,17 +9,28 @@
 // activation and the residual add into the normalize pass removes one to
 // two full tensor round-trips per block vs eager PyTorch.
 //
-// dtype: x/y/dy in T ∈ {float, bf16}; gamma/beta/stats always fp32;
-// reductions accumulate in double (N*HW can exceed 1e7 elements).
+// dtype: x/y/dy in T ∈ {float, bf16}; gamma/beta/stats always fp32.
 // Activation codes: 0 = identity, 1 = relu, 2 = relu6.
+//
+// Which kernel a shape reaches is decided once, by ddlb::bn_plan at the
+// end of this file; the launchers only switch on the plan they are given.
 
 #include "common.h"
 #include "launchers.h"
 #include <stdint.h>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
+
+using ddlb::BnElt;
+using ddlb::BnGate;
+using ddlb::BnGrid;
+using ddlb::BnPlan;
+using ddlb::BnReduce;
 
 namespace {
+
+using bf16 = __hip_bfloat16;
 
 template <int ACT> DEV float act_fwd(float v) {
   if (ACT == 1) return fmaxf(v, 0.f);
@@ -34,21 +45,145 @@ template <int ACT> DEV float act_mask(float y) {
   return 1.f;
 }
 
-}  // namespace
+// ---- W-wide lane IO: W = 1 (one element) or 8 (one 16 B / 32 B vector) --
+// NHWC: 8 consecutive elements are 8 consecutive channels (C % 8 == 0);
+// NCHW: 8 consecutive elements share one channel when HW % 8 == 0.
+typedef __attribute__((ext_vector_type(8))) short short8v;
+typedef __attribute__((ext_vector_type(8))) float float8v;
 
-// BN kernel-variant override for A/B probes (set via bindings):
-// 0 = auto, 1 = scalar-group reductions + grid-stride vector apply,
-// 2 = vector reductions + fixed-channel apply
-int g_bn_variant = 0;
-void ddlb::set_bn_variant(int v) { g_bn_variant = v; }
+template <typename T> struct vec8;
+template <> struct vec8<float> { using type = float8v; };
+template <> struct vec8<bf16> { using type = short8v; };
 
-// ---- stats: per-channel sum / sumsq over N*H*W ------------------------
-// grid = (C, S): block (c, s) covers slice s of channel c's N*HW space.
-template <typename T>
-__global__ void bn_stats_kernel(const T* __restrict__ x, double* __restrict__ sums,
-                                int64_t N, int64_t C, int64_t HW) {
+DEV float elt_f32(const short8v& v, int j) {
+  bf16 h;
+  unsigned short u = (unsigned short)v[j];
+  __builtin_memcpy(&h, &u, 2);
+  return __bfloat162float(h);
+}
+DEV float elt_f32(const float8v& v, int j) { return v[j]; }
+
+DEV void set_elt(short8v& v, int j, float f) {
+  bf16 h = __float2bfloat16(f);
+  unsigned short u;
+  __builtin_memcpy(&u, &h, 2);
+  v[j] = (short)u;
+}
+DEV void set_elt(float8v& v, int j, float f) { v[j] = f; }
+
+// W consecutive elements of one tensor, kept as loaded (bf16 stays packed)
+// and converted lane by lane where the arithmetic uses them.
+template <typename T, int W> struct Lanes;
+template <typename T> struct Lanes<T, 1> {
+  T v;
+  DEV void load(const T* __restrict__ p, int64_t vi) { v = p[vi]; }
+  DEV void store(T* __restrict__ p, int64_t vi) const { p[vi] = v; }
+  DEV float get(int) const { return to_f32(v); }
+  DEV void set(int, float f) { v = from_f32<T>(f); }
+};
+template <typename T> struct Lanes<T, 8> {
+  using V = typename vec8<T>::type;
+  V v;
+  DEV void load(const T* __restrict__ p, int64_t vi) {
+    v = reinterpret_cast<const V*>(p)[vi];
+  }
+  DEV void store(T* __restrict__ p, int64_t vi) const {
+    reinterpret_cast<V*>(p)[vi] = v;
+  }
+  DEV float get(int j) const { return elt_f32(v, j); }
+  DEV void set(int j, float f) { set_elt(v, j, f); }
+};
+
+// Activation-gradient gate of elements vi*W ..: from the 1-bit mask the
+// forward apply wrote (one byte per 8 channels; y is never read) or from
+// the output y. bit = the lane's bit in its mask byte.
+template <typename T, int W, int ACT, bool MASKED>
+struct Gate {
+  Lanes<T, W> vy;
+  unsigned mb;
+  DEV void load(const T* __restrict__ y,
+                const unsigned char* __restrict__ msk, int64_t vi) {
+    if constexpr (MASKED) mb = msk[W == 8 ? vi : vi >> 3];
+    else if constexpr (ACT != 0) vy.load(y, vi);
+  }
+  DEV float get(int j, int bit) const {
+    if constexpr (MASKED) return (float)((mb >> bit) & 1u);
+    else if constexpr (ACT != 0) return act_mask<ACT>(vy.get(j));
+    else return 1.f;
+  }
+};
+
+// ---- the two per-element terms of a reduction ---------------------------
+// Every reduce kernel sums p and p*q per channel: (x, x) for the batch
+// statistics, (dy', xhat) for the backward, dy' = dy * gate.
+template <typename T, int W>
+struct StatsTerms {
+  const T* x;
+  struct Lane {};
+  DEV Lane bind(int64_t) const { return {}; }
+  DEV void load(const Lane&, int64_t vi, float (&p)[W], float (&q)[W]) const {
+    Lanes<T, W> vx;
+    vx.load(x, vi);
+#pragma unroll
+    for (int j = 0; j < W; ++j) p[j] = q[j] = vx.get(j);
+  }
+};
+
+template <typename T, int W, int ACT, bool MASKED>
+struct BwdTerms {
+  const T* dy;
+  const T* y;
+  const T* x;
+  const float* mean;
+  const float* invstd;
+  const unsigned char* msk;
+  struct Lane { float mu[W], is[W]; int bit0; };
+  DEV Lane bind(int64_t c0) const {
+    Lane l;
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+      l.mu[j] = mean[c0 + j];
+      l.is[j] = invstd[c0 + j];
+    }
+    l.bit0 = W == 8 ? 0 : (int)(c0 & 7);
+    return l;
+  }
+  DEV void load(const Lane& l, int64_t vi, float (&p)[W],
+                float (&q)[W]) const {
+    Lanes<T, W> vdy, vx;
+    Gate<T, W, ACT, MASKED> gate;
+    vdy.load(dy, vi);
+    vx.load(x, vi);
+    gate.load(y, msk, vi);
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+      p[j] = vdy.get(j) * gate.get(j, l.bit0 + j);
+      q[j] = (vx.get(j) - l.mu[j]) * l.is[j];
+    }
+  }
+};
+
+// double accumulators (N*HW can exceed 1e7 elements per channel) ...
+DEV void accum(double& s, double& ss, float p, float q) {
+  s += p;
+  ss += fma((double)p, (double)q, 0.0);
+}
+// ... and fp32 ones for the 8-wide bf16 kernels: a thread's row slice is
+// at most a few hundred values that never were wider than fp32
+DEV void accum(float& s, float& ss, float p, float q) {
+  s += p;
+  ss = fmaf(p, q, ss);
+}
+
+// ---- reduce, NCHW -------------------------------------------------------
+// grid = (C, S): block (c, s) covers slice s of channel c's N*HW space and
+// writes its two sums to slab s of sums[S][2][C].
+template <typename Terms>
+__global__ void bn_reduce_nchw_kernel(Terms terms, double* __restrict__ sums,
+                                      int64_t N, int64_t C, int64_t HW) {
   __shared__ double tmp[8];
   const int64_t c = blockIdx.x;
+  const auto lane = terms.bind(c);
   const int64_t total = N * HW;
   const int64_t per = (total + gridDim.y - 1) / gridDim.y;
   const int64_t begin = (int64_t)blockIdx.y * per;
@@ -56,9 +191,9 @@ __global__ void bn_stats_kernel(const T* __restrict__ x, double* __restrict__ su
   double s = 0.0, ss = 0.0;
   for (int64_t i = begin + threadIdx.x; i < end; i += blockDim.x) {
     const int64_t n = i / HW, r = i - n * HW;
-    const float v = to_f32(x[(n * C + c) * HW + r]);
-    s += v;
-    ss += fma((double)v, (double)v, 0.0);
+    float p[1], q[1];
+    terms.load(lane, (n * C + c) * HW + r, p, q);
+    accum(s, ss, p[0], q[0]);
   }
   auto op = [](double v) { return wave_reduce_sum(v); };
   s = block_reduce(s, tmp, op, 0.0);
@@ -70,95 +205,55 @@ __global__ void bn_stats_kernel(const T* __restrict__ x, double* __restrict__ su
   }
 }
 
-// ---- stats, NHWC (channels-last) --------------------------------------
-// rows = N*H*W; element (row, c) at row*C + c. Block = CG channels x
-// (256/CG) row-groups: every wave reads consecutive channels of one row
-// (coalesced), the row-groups + a 4x unroll keep >=16 rows in flight per
-// block; per-channel partials combine across row-groups in LDS, one f64
-// atomic per channel per block.
-template <typename T>
-__global__ void bn_stats_nhwc_kernel(const T* __restrict__ x,
-                                     double* __restrict__ sums,
-                                     int64_t rows, int64_t C, int CG) {
-  __shared__ double tmp[2 * 256];
+// ---- reduce, NHWC (channels-last) ---------------------------------------
+// rows = N*H*W; element (row, c) at row*C + c. Block = CG channel lanes of
+// W channels each x (256/CG) row-groups; grid = (lane blocks, S row
+// slices). Every wave reads consecutive channels of one row (coalesced);
+// per-thread partials of type AT combine across row-groups in LDS, in
+// row-group order, and land in slab blockIdx.y of sums[S][2][C] with plain
+// stores. W = 8: one 16 B bf16 vector per lane, fp32 partials and slabs.
+// W = 1: double partials and slabs. UNROLL4 is the scalar statistics
+// kernel's summation order: four rows are added to each other first and
+// then to the running sum.
+template <int W, typename AT, bool UNROLL4, typename Terms>
+__global__ void bn_reduce_nhwc_kernel(Terms terms, AT* __restrict__ sums,
+                                      int64_t rows, int64_t C, int CG) {
+  static_assert(!UNROLL4 || W == 1, "the 4-row order is a scalar one");
+  __shared__ AT tmp[2][256][W];
   const int ci = threadIdx.x % CG;
   const int rj = threadIdx.x / CG;
   const int RG = blockDim.x / CG;
-  const int64_t c = (int64_t)blockIdx.x * CG + ci;
-  const bool active = (c < C) && (rj < RG);
-  const int64_t per = (rows + gridDim.y - 1) / gridDim.y;
-  const int64_t begin = (int64_t)blockIdx.y * per;
-  const int64_t end = i64min(begin + per, rows);
-  double s = 0.0, ss = 0.0;
-  if (active) {
-    int64_t r = begin + rj;
-    const int64_t step = RG;
-    for (; r + 3 * step < end; r += 4 * step) {
-      float v0 = to_f32(x[(r + 0 * step) * C + c]);
-      float v1 = to_f32(x[(r + 1 * step) * C + c]);
-      float v2 = to_f32(x[(r + 2 * step) * C + c]);
-      float v3 = to_f32(x[(r + 3 * step) * C + c]);
-      s += (double)v0 + v1 + v2 + v3;
-      ss += fma((double)v0, v0, fma((double)v1, v1,
-                fma((double)v2, v2, (double)v3 * v3)));
-    }
-    for (; r < end; r += step) {
-      const float v = to_f32(x[r * C + c]);
-      s += v;
-      ss += fma((double)v, (double)v, 0.0);
-    }
-  }
-  tmp[threadIdx.x] = s;
-  tmp[256 + threadIdx.x] = ss;
-  __syncthreads();
-  if (rj == 0 && c < C) {
-    for (int j = 1; j < RG; ++j) {
-      s += tmp[j * CG + ci];
-      ss += tmp[256 + j * CG + ci];
-    }
-    sums[((int64_t)blockIdx.y * 2 + 0) * C + c] = s;
-    sums[((int64_t)blockIdx.y * 2 + 1) * C + c] = ss;
-  }
-}
-
-// ---- stats, NHWC vectorized: 8 channels (16 B) per lane --------------
-// Each thread covers channels c0..c0+7 of CG8*8-channel groups; f32
-// per-thread partials over a short row slice (<= a few hundred values)
-// combine in LDS across row-groups and land in an fp32 slab (the values
-// never were wider than fp32).
-template <typename T>
-__global__ void bn_stats_nhwc_vec_kernel(const T* __restrict__ x,
-                                         float* __restrict__ sums,
-                                         int64_t rows, int64_t C, int CG8) {
-  typedef __attribute__((ext_vector_type(8))) short short8x;
-  __shared__ float tmp[2][256][8];
-  const int ci = threadIdx.x % CG8;
-  const int rj = threadIdx.x / CG8;
-  const int RG = blockDim.x / CG8;
-  const int64_t c0 = ((int64_t)blockIdx.x * CG8 + ci) * 8;
+  const int64_t c0 = ((int64_t)blockIdx.x * CG + ci) * W;
   const bool active = (c0 < C) && (rj < RG);
   const int64_t per = (rows + gridDim.y - 1) / gridDim.y;
   const int64_t begin = (int64_t)blockIdx.y * per;
   const int64_t end = i64min(begin + per, rows);
-  float s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  float ss[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  AT s[W] = {}, ss[W] = {};
   if (active) {
-    const short8x* xv = reinterpret_cast<const short8x*>(x);
-    for (int64_t r = begin + rj; r < end; r += RG) {
-      short8x v = xv[(r * C + c0) / 8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        __hip_bfloat16 h;
-        unsigned short u = (unsigned short)v[j];
-        __builtin_memcpy(&h, &u, 2);
-        const float f = __bfloat162float(h);
-        s[j] += f;
-        ss[j] = fmaf(f, f, ss[j]);
+    const auto lane = terms.bind(c0);
+    int64_t r = begin + rj;
+    const int64_t step = RG;
+    if constexpr (UNROLL4) {
+      for (; r + 3 * step < end; r += 4 * step) {
+        float p0[1], p1[1], p2[1], p3[1], q0[1], q1[1], q2[1], q3[1];
+        terms.load(lane, (r + 0 * step) * C + c0, p0, q0);
+        terms.load(lane, (r + 1 * step) * C + c0, p1, q1);
+        terms.load(lane, (r + 2 * step) * C + c0, p2, q2);
+        terms.load(lane, (r + 3 * step) * C + c0, p3, q3);
+        s[0] += (double)p0[0] + p1[0] + p2[0] + p3[0];
+        ss[0] += fma((double)p0[0], q0[0], fma((double)p1[0], q1[0],
+                     fma((double)p2[0], q2[0], (double)p3[0] * q3[0])));
       }
+    }
+    for (; r < end; r += step) {
+      float p[W], q[W];
+      terms.load(lane, (r * C + c0) / W, p, q);
+#pragma unroll
+      for (int j = 0; j < W; ++j) accum(s[j], ss[j], p[j], q[j]);
     }
   }
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
+  for (int j = 0; j < W; ++j) {
     tmp[0][threadIdx.x][j] = s[j];
     tmp[1][threadIdx.x][j] = ss[j];
   }
@@ -166,65 +261,19 @@ __global__ void bn_stats_nhwc_vec_kernel(const T* __restrict__ x,
   if (rj == 0 && c0 < C) {
     for (int g = 1; g < RG; ++g)
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        s[j] += tmp[0][g * CG8 + ci][j];
-        ss[j] += tmp[1][g * CG8 + ci][j];
+      for (int j = 0; j < W; ++j) {
+        s[j] += tmp[0][g * CG + ci][j];
+        ss[j] += tmp[1][g * CG + ci][j];
       }
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
+    for (int j = 0; j < W; ++j) {
       sums[((int64_t)blockIdx.y * 2 + 0) * C + c0 + j] = s[j];
       sums[((int64_t)blockIdx.y * 2 + 1) * C + c0 + j] = ss[j];
     }
   }
 }
 
-// fp32 NHWC vec stats (4 channels / 16 B)
-__global__ void bn_stats_nhwc_vec_f32_kernel(const float* __restrict__ x,
-                                             double* __restrict__ sums,
-                                             int64_t rows, int64_t C,
-                                             int CG4) {
-  typedef __attribute__((ext_vector_type(4))) float float4x;
-  __shared__ float tmp[2][256][4];
-  const int ci = threadIdx.x % CG4;
-  const int rj = threadIdx.x / CG4;
-  const int RG = blockDim.x / CG4;
-  const int64_t c0 = ((int64_t)blockIdx.x * CG4 + ci) * 4;
-  const bool active = (c0 < C) && (rj < RG);
-  const int64_t per = (rows + gridDim.y - 1) / gridDim.y;
-  const int64_t begin = (int64_t)blockIdx.y * per;
-  const int64_t end = i64min(begin + per, rows);
-  float s[4] = {0, 0, 0, 0}, ss[4] = {0, 0, 0, 0};
-  if (active) {
-    const float4x* xv = reinterpret_cast<const float4x*>(x);
-    for (int64_t r = begin + rj; r < end; r += RG) {
-      float4x v = xv[(r * C + c0) / 4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        s[j] += v[j];
-        ss[j] = fmaf(v[j], v[j], ss[j]);
-      }
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    tmp[0][threadIdx.x][j] = s[j];
-    tmp[1][threadIdx.x][j] = ss[j];
-  }
-  __syncthreads();
-  if (rj == 0 && c0 < C) {
-    for (int g = 1; g < RG; ++g)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        s[j] += tmp[0][g * CG4 + ci][j];
-        ss[j] += tmp[1][g * CG4 + ci][j];
-      }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      sums[((int64_t)blockIdx.y * 2 + 0) * C + c0 + j] = (double)s[j];
-      sums[((int64_t)blockIdx.y * 2 + 1) * C + c0 + j] = (double)ss[j];
-    }
-  }
-}
+}  // namespace
 
 // ---- finalize: slabs -> per-channel results, one launch ----------------
 // sums = per-(row-slice) partial slabs [S][2][C] written with plain
@@ -383,8 +432,14 @@ void bn_finalize_kernel(BnFinParams q) {
   }
 }
 
-// ---- apply: y = act(gamma*(x-mean)*invstd + beta [+ res]) -------------
-template <typename T, int ACT, bool ADD>
+namespace {
+
+// ---- apply / dx, grid-stride --------------------------------------------
+// y = act(gamma*(x-mean)*invstd + beta [+ res]);
+// dx = k1 * (dy' - k2 - xhat*k3), optionally dres = dy'.
+// Thread i handles elements i*W ..; LANE_CH: lane j has channel
+// (i*W) % C + j (NHWC vectors), otherwise all W share (i*W / cdiv) % C.
+template <typename T, int W, int ACT, bool ADD, bool LANE_CH>
 __global__ void bn_apply_kernel(const T* __restrict__ x,
                                 const T* __restrict__ res,
                                 T* __restrict__ y,
@@ -392,148 +447,72 @@ __global__ void bn_apply_kernel(const T* __restrict__ x,
                                 const float* __restrict__ invstd,
                                 const float* __restrict__ gamma,
                                 const float* __restrict__ beta,
-                                int64_t C, int64_t cdiv, int64_t total) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += stride) {
-    const int64_t c = (i / cdiv) % C;
-    float v = (to_f32(x[i]) - mean[c]) * invstd[c] * gamma[c] + beta[c];
-    if (ADD) v += to_f32(res[i]);
-    y[i] = from_f32<T>(act_fwd<ACT>(v));
-  }
-}
-
-// ---- vectorized apply / dx: 8 elements (16 B) per thread -------------
-// NHWC: 8 consecutive elements are 8 consecutive channels (chunks are
-// 8-aligned in c when C %% 8 == 0); NCHW: 8 consecutive elements share
-// one channel when HW %% 8 == 0. Dispatcher falls back to the scalar
-// kernels otherwise.
-typedef __attribute__((ext_vector_type(8))) short short8v;
-typedef __attribute__((ext_vector_type(4))) float float4v;
-
-template <typename T> struct vec8;
-template <> struct vec8<float> {
-  using type = __attribute__((ext_vector_type(8))) float;
-};
-template <> struct vec8<__hip_bfloat16> { using type = short8v; };
-
-DEV float elt_f32(const short8v& v, int j) {
-  __hip_bfloat16 h;
-  unsigned short u = (unsigned short)v[j];
-  __builtin_memcpy(&h, &u, 2);
-  return __bfloat162float(h);
-}
-DEV float elt_f32(const __attribute__((ext_vector_type(8))) float& v,
-                  int j) { return v[j]; }
-
-template <typename T>
-DEV void set_elt(short8v& v, int j, float f) {
-  __hip_bfloat16 h = __float2bfloat16(f);
-  unsigned short u;
-  __builtin_memcpy(&u, &h, 2);
-  v[j] = (short)u;
-}
-template <typename T>
-DEV void set_elt(__attribute__((ext_vector_type(8))) float& v, int j,
-                 float f) { v[j] = f; }
-
-template <typename T, int ACT, bool ADD, bool NHWC>
-__global__ void bn_apply_vec_kernel(const T* __restrict__ x,
-                                    const T* __restrict__ res,
-                                    T* __restrict__ y,
-                                    const float* __restrict__ mean,
-                                    const float* __restrict__ invstd,
-                                    const float* __restrict__ gamma,
-                                    const float* __restrict__ beta,
-                                    int64_t C, int64_t cdiv,
-                                    int64_t total8) {
-  using V = typename vec8<T>::type;
-  const V* xv = reinterpret_cast<const V*>(x);
-  const V* rv = reinterpret_cast<const V*>(res);
-  V* yv = reinterpret_cast<V*>(y);
+                                int64_t C, int64_t cdiv, int64_t totalW) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-       i < total8; i += stride) {
-    const int64_t e0 = i * 8;
-    V vx = xv[i];
-    V vr;
-    if (ADD) vr = rv[i];
-    V vy;
-    if (NHWC) {
-      const int64_t c0 = e0 % C;
+       i < totalW; i += stride) {
+    const int64_t e0 = i * W;
+    const int64_t cb = LANE_CH ? e0 % C : (e0 / cdiv) % C;
+    Lanes<T, W> vx, vr, vy;
+    vx.load(x, i);
+    if (ADD) vr.load(res, i);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int64_t c = c0 + j;
-        float v = (elt_f32(vx, j) - mean[c]) * invstd[c] * gamma[c]
-                  + beta[c];
-        if (ADD) v += elt_f32(vr, j);
-        set_elt<T>(vy, j, act_fwd<ACT>(v));
-      }
-    } else {
-      const int64_t c = (e0 / cdiv) % C;
-      const float mu = mean[c], is = invstd[c], g = gamma[c], b = beta[c];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float v = (elt_f32(vx, j) - mu) * is * g + b;
-        if (ADD) v += elt_f32(vr, j);
-        set_elt<T>(vy, j, act_fwd<ACT>(v));
-      }
+    for (int j = 0; j < W; ++j) {
+      const int64_t c = LANE_CH ? cb + j : cb;
+      float v = (vx.get(j) - mean[c]) * invstd[c] * gamma[c] + beta[c];
+      if (ADD) v += vr.get(j);
+      vy.set(j, act_fwd<ACT>(v));
     }
-    yv[i] = vy;
+    vy.store(y, i);
   }
 }
 
-template <typename T, int ACT, bool ADD, bool NHWC>
-__global__ void bn_bwd_dx_vec_kernel(const T* __restrict__ dy,
-                                     const T* __restrict__ y,
-                                     const T* __restrict__ x,
-                                     const float* __restrict__ mean,
-                                     const float* __restrict__ invstd,
-                                     const float* __restrict__ k,
-                                     T* __restrict__ dx,
-                                     T* __restrict__ dres, int64_t C,
-                                     int64_t cdiv, int64_t total8) {
-  using V = typename vec8<T>::type;
-  const V* dyv = reinterpret_cast<const V*>(dy);
-  const V* yv = reinterpret_cast<const V*>(y);
-  const V* xv = reinterpret_cast<const V*>(x);
-  V* dxv = reinterpret_cast<V*>(dx);
-  V* drv = reinterpret_cast<V*>(dres);
+template <typename T, int W, int ACT, bool ADD, bool LANE_CH>
+__global__ void bn_bwd_dx_kernel(const T* __restrict__ dy,
+                                 const T* __restrict__ y,
+                                 const T* __restrict__ x,
+                                 const float* __restrict__ mean,
+                                 const float* __restrict__ invstd,
+                                 const float* __restrict__ k,
+                                 T* __restrict__ dx, T* __restrict__ dres,
+                                 int64_t C, int64_t cdiv, int64_t totalW) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-       i < total8; i += stride) {
-    const int64_t e0 = i * 8;
-    V vdy = dyv[i], vy = yv[i], vx = xv[i];
-    V vdx, vdr;
+       i < totalW; i += stride) {
+    const int64_t e0 = i * W;
+    Lanes<T, W> vdy, vx, vdx, vdr;
+    Gate<T, W, ACT, false> gate;
+    vdy.load(dy, i);
+    gate.load(y, nullptr, i);
+    vx.load(x, i);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int64_t c = NHWC ? (e0 % C + j) : ((e0 / cdiv) % C);
-      const float g = elt_f32(vdy, j) * act_mask<ACT>(elt_f32(vy, j));
-      const float xhat = (elt_f32(vx, j) - mean[c]) * invstd[c];
-      set_elt<T>(vdx, j, k[c] * (g - k[C + c] - xhat * k[2 * C + c]));
-      if (ADD) set_elt<T>(vdr, j, g);
+    for (int j = 0; j < W; ++j) {
+      const int64_t c = LANE_CH ? (e0 % C + j) : ((e0 / cdiv) % C);
+      const float g = vdy.get(j) * gate.get(j, j);
+      const float xhat = (vx.get(j) - mean[c]) * invstd[c];
+      vdx.set(j, k[c] * (g - k[C + c] - xhat * k[2 * C + c]));
+      if (ADD) vdr.set(j, g);
     }
-    dxv[i] = vdx;
-    if (ADD) drv[i] = vdr;
+    vdx.store(dx, i);
+    if (ADD) vdr.store(dres, i);
   }
 }
 
-// ---- NHWC apply / dx, fixed-channel geometry ---------------------------
+// ---- NHWC bf16 apply / dx, fixed-channel geometry -------------------------
 // Same (CG8 x RG) block shape as the reductions: each thread owns 8
 // channels and walks rows, so per-channel params load ONCE per thread
 // instead of once per element (the grid-stride variant is issue-bound
 // on the 32 extra scalar loads per 48 B of traffic).
-template <typename T, int ACT, bool ADD>
-__global__ void bn_apply_nhwc_kernel2(const T* __restrict__ x,
-                                      const T* __restrict__ res,
-                                      T* __restrict__ y,
+template <int ACT, bool ADD>
+__global__ void bn_apply_fixed_kernel(const bf16* __restrict__ x,
+                                      const bf16* __restrict__ res,
+                                      bf16* __restrict__ y,
                                       const float* __restrict__ mean,
                                       const float* __restrict__ invstd,
                                       const float* __restrict__ gamma,
                                       const float* __restrict__ beta,
                                       unsigned char* __restrict__ msk,
                                       int64_t rows, int64_t C, int CG8) {
-  typedef __attribute__((ext_vector_type(8))) short short8x;
   const int ci = threadIdx.x % CG8;
   const int rj = threadIdx.x / CG8;
   const int RG = blockDim.x / CG8;
@@ -548,54 +527,36 @@ __global__ void bn_apply_nhwc_kernel2(const T* __restrict__ x,
   const int64_t per = (rows + gridDim.y - 1) / gridDim.y;
   const int64_t begin = (int64_t)blockIdx.y * per;
   const int64_t end = i64min(begin + per, rows);
-  const short8x* xv = reinterpret_cast<const short8x*>(x);
-  const short8x* rv = reinterpret_cast<const short8x*>(res);
-  short8x* yv = reinterpret_cast<short8x*>(y);
   for (int64_t r = begin + rj; r < end; r += RG) {
     const int64_t i8 = (r * C + c0) / 8;
-    short8x vx = xv[i8];
-    short8x vr;
-    if (ADD) vr = rv[i8];
-    short8x vy;
+    Lanes<bf16, 8> vx, vr, vy;
+    vx.load(x, i8);
+    if (ADD) vr.load(res, i8);
     unsigned mbits = 0;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      __hip_bfloat16 h;
-      unsigned short u = (unsigned short)vx[j];
-      __builtin_memcpy(&h, &u, 2);
-      float v = fmaf(__bfloat162float(h), sc[j], sh[j]);
-      if (ADD) {
-        u = (unsigned short)vr[j];
-        __builtin_memcpy(&h, &u, 2);
-        v += __bfloat162float(h);
-      }
+      float v = fmaf(vx.get(j), sc[j], sh[j]);
+      if (ADD) v += vr.get(j);
       if (ACT != 0 && act_mask<ACT>(v) > 0.f) mbits |= 1u << j;
-      h = __float2bfloat16(act_fwd<ACT>(v));
-      __builtin_memcpy(&u, &h, 2);
-      vy[j] = (short)u;
+      vy.set(j, act_fwd<ACT>(v));
     }
-    yv[i8] = vy;
+    vy.store(y, i8);
     // 1-bit activation mask: backward re-reads this byte instead of y
-    // (docs/ROADMAP.md item 7: ~2 of 7 memory passes saved)
     if (ACT != 0 && msk != nullptr) msk[i8] = (unsigned char)mbits;
   }
 }
 
-// MASKED: the activation gradient gate comes from the 1-bit mask the
-// forward apply wrote (one byte per 8 channels); y is never read.
-template <typename T, int ACT, bool ADD, bool MASKED = false>
-__global__ void bn_bwd_dx_nhwc_kernel2(const T* __restrict__ dy,
-                                       const T* __restrict__ y,
-                                       const T* __restrict__ x,
+template <int ACT, bool ADD, bool MASKED>
+__global__ void bn_bwd_dx_fixed_kernel(const bf16* __restrict__ dy,
+                                       const bf16* __restrict__ y,
+                                       const bf16* __restrict__ x,
                                        const float* __restrict__ mean,
                                        const float* __restrict__ invstd,
                                        const float* __restrict__ k,
-                                       T* __restrict__ dx,
-                                       T* __restrict__ dres,
+                                       bf16* __restrict__ dx,
+                                       bf16* __restrict__ dres,
                                        const unsigned char* __restrict__ msk,
-                                       int64_t rows,
-                                       int64_t C, int CG8) {
-  typedef __attribute__((ext_vector_type(8))) short short8x;
+                                       int64_t rows, int64_t C, int CG8) {
   const int ci = threadIdx.x % CG8;
   const int rj = threadIdx.x / CG8;
   const int RG = blockDim.x / CG8;
@@ -613,316 +574,212 @@ __global__ void bn_bwd_dx_nhwc_kernel2(const T* __restrict__ dy,
   const int64_t per = (rows + gridDim.y - 1) / gridDim.y;
   const int64_t begin = (int64_t)blockIdx.y * per;
   const int64_t end = i64min(begin + per, rows);
-  const short8x* dyv = reinterpret_cast<const short8x*>(dy);
-  const short8x* yv = reinterpret_cast<const short8x*>(y);
-  const short8x* xv = reinterpret_cast<const short8x*>(x);
-  short8x* dxv = reinterpret_cast<short8x*>(dx);
-  short8x* drv = reinterpret_cast<short8x*>(dres);
   for (int64_t r = begin + rj; r < end; r += RG) {
     const int64_t i8 = (r * C + c0) / 8;
-    short8x vdy = dyv[i8], vx = xv[i8];
-    short8x vy;
-    unsigned mb = 0;
-    if (MASKED) mb = msk[i8];
-    else vy = yv[i8];
-    short8x vdx, vdr;
+    Lanes<bf16, 8> vdy, vx, vdx, vdr;
+    Gate<bf16, 8, ACT, MASKED> gate;
+    vdy.load(dy, i8);
+    vx.load(x, i8);
+    gate.load(y, msk, i8);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      __hip_bfloat16 h;
-      unsigned short u;
-      u = (unsigned short)vdy[j];
-      __builtin_memcpy(&h, &u, 2);
-      const float fdy = __bfloat162float(h);
-      float gate;
-      if (MASKED) {
-        gate = (float)((mb >> j) & 1u);
-      } else {
-        u = (unsigned short)vy[j];
-        __builtin_memcpy(&h, &u, 2);
-        gate = act_mask<ACT>(__bfloat162float(h));
-      }
-      u = (unsigned short)vx[j];
-      __builtin_memcpy(&h, &u, 2);
-      const float fx = __bfloat162float(h);
-      const float g = fdy * gate;
-      const float xhat = (fx - mu[j]) * is[j];
-      h = __float2bfloat16(k1[j] * (g - k2[j] - xhat * k3[j]));
-      __builtin_memcpy(&u, &h, 2);
-      vdx[j] = (short)u;
-      if (ADD) {
-        h = __float2bfloat16(g);
-        __builtin_memcpy(&u, &h, 2);
-        vdr[j] = (short)u;
-      }
+      const float g = vdy.get(j) * gate.get(j, j);
+      const float xhat = (vx.get(j) - mu[j]) * is[j];
+      vdx.set(j, k1[j] * (g - k2[j] - xhat * k3[j]));
+      if (ADD) vdr.set(j, g);
     }
-    dxv[i8] = vdx;
-    if (ADD) drv[i8] = vdr;
+    vdx.store(dx, i8);
+    if (ADD) vdr.store(dres, i8);
   }
 }
 
-// ---- backward reduce: per-channel Σdy', Σdy'*xhat ---------------------
-template <typename T, int ACT>
-__global__ void bn_bwd_reduce_kernel(const T* __restrict__ dy,
-                                     const T* __restrict__ y,
-                                     const T* __restrict__ x,
-                                     const float* __restrict__ mean,
-                                     const float* __restrict__ invstd,
-                                     double* __restrict__ sums,
-                                     int64_t N, int64_t C, int64_t HW) {
-  __shared__ double tmp[8];
-  const int64_t c = blockIdx.x;
-  const float mu = mean[c], is = invstd[c];
-  const int64_t total = N * HW;
-  const int64_t per = (total + gridDim.y - 1) / gridDim.y;
-  const int64_t begin = (int64_t)blockIdx.y * per;
-  const int64_t end = i64min(begin + per, total);
-  double sdy = 0.0, sdyx = 0.0;
-  for (int64_t i = begin + threadIdx.x; i < end; i += blockDim.x) {
-    const int64_t n = i / HW, r = i - n * HW;
-    const int64_t idx = (n * C + c) * HW + r;
-    const float g = to_f32(dy[idx]) * act_mask<ACT>(to_f32(y[idx]));
-    const float xhat = (to_f32(x[idx]) - mu) * is;
-    sdy += g;
-    sdyx += fma((double)g, (double)xhat, 0.0);
-  }
-  auto op = [](double v) { return wave_reduce_sum(v); };
-  sdy = block_reduce(sdy, tmp, op, 0.0);
-  __syncthreads();
-  sdyx = block_reduce(sdyx, tmp, op, 0.0);
-  if (threadIdx.x == 0) {
-    sums[((int64_t)blockIdx.y * 2 + 0) * C + c] = sdy;
-    sums[((int64_t)blockIdx.y * 2 + 1) * C + c] = sdyx;
-  }
-}
+// ---- dispatch plan --------------------------------------------------------
+// The tuning constants of the whole family; re-tuning one is an edit here,
+// measured with benchmark/bn_probe.py against the previous build.
+constexpr int BN_BLOCK = 256;             // threads per block, all kernels
+constexpr int64_t BN_LANES = 64;          // channel lanes per NHWC block
+// 8-wide bf16 reduces up to this C (the probe shows them ahead there)
+constexpr int64_t BN_VEC_REDUCE_MAX_C = 512;
+// the fixed-channel apply/dx starve below this many rows (too few blocks)
+constexpr int64_t BN_FIXED_MIN_ROWS = 32768;
+// rows/16 (not /512): a block still covers >=16 rows per row-group, and
+// the old cap starved the small-HW layers (C2048@7x7 ran 196 blocks on a
+// 256-CU chip)
+constexpr int64_t BN_ROWS_PER_SLICE = 16;
+constexpr int64_t BN_MAX_BLOCKS = 2048;   // reduce / fixed-channel grids
+constexpr int64_t BN_ELT_MAX_BLOCKS = 256 * 8;  // grid-stride grids
 
-// ---- backward reduce, NHWC (same block geometry as the stats) ---------
-template <typename T, int ACT, bool MASKED = false>
-__global__ void bn_bwd_reduce_nhwc_kernel(const T* __restrict__ dy,
-                                          const T* __restrict__ y,
-                                          const T* __restrict__ x,
-                                          const float* __restrict__ mean,
-                                          const float* __restrict__ invstd,
-                                          double* __restrict__ sums,
-                                          const unsigned char* __restrict__
-                                              msk,
-                                          int64_t rows, int64_t C, int CG) {
-  __shared__ double tmp[2 * 256];
-  const int ci = threadIdx.x % CG;
-  const int rj = threadIdx.x / CG;
-  const int RG = blockDim.x / CG;
-  const int64_t c = (int64_t)blockIdx.x * CG + ci;
-  const bool active = (c < C) && (rj < RG);
-  const int64_t per = (rows + gridDim.y - 1) / gridDim.y;
-  const int64_t begin = (int64_t)blockIdx.y * per;
-  const int64_t end = i64min(begin + per, rows);
-  double sdy = 0.0, sdyx = 0.0;
-  if (active) {
-    const float mu = mean[c], is = invstd[c];
-    const int cbit = (int)(c & 7);
-    for (int64_t r = begin + rj; r < end; r += RG) {
-      const int64_t idx = r * C + c;
-      float gate;
-      if (MASKED)
-        gate = (float)((msk[idx >> 3] >> cbit) & 1u);
-      else
-        gate = act_mask<ACT>(to_f32(y[idx]));
-      const float g = to_f32(dy[idx]) * gate;
-      const float xhat = (to_f32(x[idx]) - mu) * is;
-      sdy += g;
-      sdyx += fma((double)g, (double)xhat, 0.0);
-    }
-  }
-  tmp[threadIdx.x] = sdy;
-  tmp[256 + threadIdx.x] = sdyx;
-  __syncthreads();
-  if (rj == 0 && c < C) {
-    for (int j = 1; j < RG; ++j) {
-      sdy += tmp[j * CG + ci];
-      sdyx += tmp[256 + j * CG + ci];
-    }
-    sums[((int64_t)blockIdx.y * 2 + 0) * C + c] = sdy;
-    sums[((int64_t)blockIdx.y * 2 + 1) * C + c] = sdyx;
-  }
-}
-
-template <typename T, int ACT, bool MASKED = false>
-__global__ void bn_bwd_reduce_nhwc_vec_kernel(
-    const T* __restrict__ dy, const T* __restrict__ y,
-    const T* __restrict__ x, const float* __restrict__ mean,
-    const float* __restrict__ invstd, float* __restrict__ sums,
-    const unsigned char* __restrict__ msk,
-    int64_t rows, int64_t C, int CG8) {
-  typedef __attribute__((ext_vector_type(8))) short short8x;
-  __shared__ float tmp[2][256][8];
-  const int ci = threadIdx.x % CG8;
-  const int rj = threadIdx.x / CG8;
-  const int RG = blockDim.x / CG8;
-  const int64_t c0 = ((int64_t)blockIdx.x * CG8 + ci) * 8;
-  const bool active = (c0 < C) && (rj < RG);
-  const int64_t per = (rows + gridDim.y - 1) / gridDim.y;
-  const int64_t begin = (int64_t)blockIdx.y * per;
-  const int64_t end = i64min(begin + per, rows);
-  float sdy[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  float sdyx[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  float mu[8], is[8];
-  if (active) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      mu[j] = mean[c0 + j];
-      is[j] = invstd[c0 + j];
-    }
-    const short8x* dyv = reinterpret_cast<const short8x*>(dy);
-    const short8x* yv = reinterpret_cast<const short8x*>(y);
-    const short8x* xv = reinterpret_cast<const short8x*>(x);
-    for (int64_t r = begin + rj; r < end; r += RG) {
-      const int64_t i8 = (r * C + c0) / 8;
-      short8x vdy = dyv[i8], vx = xv[i8];
-      short8x vy;
-      unsigned mb = 0;
-      if (MASKED) mb = msk[i8];
-      else vy = yv[i8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        __hip_bfloat16 h;
-        unsigned short u;
-        u = (unsigned short)vdy[j];
-        __builtin_memcpy(&h, &u, 2);
-        const float fdy = __bfloat162float(h);
-        float gate;
-        if (MASKED) {
-          gate = (float)((mb >> j) & 1u);
-        } else {
-          u = (unsigned short)vy[j];
-          __builtin_memcpy(&h, &u, 2);
-          gate = act_mask<ACT>(__bfloat162float(h));
-        }
-        u = (unsigned short)vx[j];
-        __builtin_memcpy(&h, &u, 2);
-        const float fx = __bfloat162float(h);
-        const float g = fdy * gate;
-        sdy[j] += g;
-        sdyx[j] = fmaf(g, (fx - mu[j]) * is[j], sdyx[j]);
-      }
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    tmp[0][threadIdx.x][j] = sdy[j];
-    tmp[1][threadIdx.x][j] = sdyx[j];
-  }
-  __syncthreads();
-  if (rj == 0 && c0 < C) {
-    for (int g = 1; g < RG; ++g)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        sdy[j] += tmp[0][g * CG8 + ci][j];
-        sdyx[j] += tmp[1][g * CG8 + ci][j];
-      }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      sums[((int64_t)blockIdx.y * 2 + 0) * C + c0 + j] = sdy[j];
-      sums[((int64_t)blockIdx.y * 2 + 1) * C + c0 + j] = sdyx[j];
-    }
-  }
-}
-
-// dx = k1 * (dy' - k2 - xhat*k3); optionally dres = dy'
-template <typename T, int ACT, bool ADD>
-__global__ void bn_bwd_dx_kernel(const T* __restrict__ dy,
-                                 const T* __restrict__ y,
-                                 const T* __restrict__ x,
-                                 const float* __restrict__ mean,
-                                 const float* __restrict__ invstd,
-                                 const float* __restrict__ k,
-                                 T* __restrict__ dx, T* __restrict__ dres,
-                                 int64_t C, int64_t cdiv, int64_t total) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += stride) {
-    const int64_t c = (i / cdiv) % C;
-    const float g = to_f32(dy[i]) * act_mask<ACT>(to_f32(y[i]));
-    const float xhat = (to_f32(x[i]) - mean[c]) * invstd[c];
-    dx[i] = from_f32<T>(k[c] * (g - k[C + c] - xhat * k[2 * C + c]));
-    if (ADD) dres[i] = from_f32<T>(g);
-  }
-}
-
-// ---- launchers --------------------------------------------------------
-static inline int elementwise_grid(int64_t total, int block) {
-  int64_t want = (total + block - 1) / block;
-  return (int)i64min(want > 0 ? want : 1, 256 * 8);
-}
-
-
-// Reduction-kernel dispatch geometry, shared by the launchers AND the
-// workspace sizing in the bindings through bn_workspace_plan (partial
-// slab = [S][2][C], fp32 from the bf16 vec kernels, else double).
-// g_bn_variant: 0 = shape-adaptive (vec reductions for C <= 512 where
-// the probe shows them ahead), 1 = scalar, 2 = vec.
-struct BnGeom { bool vec; int64_t cblocks, S; };
-
-static BnGeom bn_reduce_geom(int64_t rows, int64_t C, int elsize) {
-  BnGeom g;
-  const bool vec_ok = (elsize == 2 && C % 8 == 0) ||
-                      (elsize == 4 && C % 4 == 0);
-  g.vec = vec_ok && (g_bn_variant == 2 ||
-                     (g_bn_variant == 0 && C <= 512 && elsize == 2));
-  if (g.vec) {
-    const int64_t lanes = elsize == 2 ? C / 8 : C / 4;
-    const int64_t CG = i64min(lanes, 64);
-    g.cblocks = (lanes + CG - 1) / CG;
-  } else {
-    const int64_t CG = C >= 64 ? 64 : C;
-    g.cblocks = (C + CG - 1) / CG;
-  }
-  // rows/16 (not /512): a block still covers >=16 rows per row-group,
-  // and the old cap starved the small-HW layers (C2048@7x7 ran 196
-  // blocks on a 256-CU chip)
-  g.S = i64min(i64max(rows / 16, 1), i64max(2048 / g.cblocks, 1));
+// (lane blocks, row slices) of the NHWC kernels whose threads own channels
+BnGrid row_grid(int64_t rows, int64_t lanes) {
+  const int64_t cg = i64min(lanes, BN_LANES);
+  BnGrid g;
+  g.x = (lanes + cg - 1) / cg;
+  g.y = i64min(i64max(rows / BN_ROWS_PER_SLICE, 1),
+               i64max(BN_MAX_BLOCKS / g.x, 1));
   return g;
 }
 
-int64_t ddlb::bn_reduce_gridS(int64_t N, int64_t C, int64_t HW, int nhwc,
-                              int elsize) {
-  if (nhwc) return bn_reduce_geom(N * HW, C, elsize).S;
-  int64_t S = i64min((N * HW + 255) / 256, i64max(2048 / C, 1));
-  return i64max(S, 1);
+BnGrid elementwise_grid(int64_t total) {
+  const int64_t want = (total + BN_BLOCK - 1) / BN_BLOCK;
+  return {i64min(want > 0 ? want : 1, BN_ELT_MAX_BLOCKS), 1};
 }
 
-// fp32 slabs exactly where the bf16 vec reduce kernels run
-static bool bn_slab_f32(int64_t rows, int64_t C, int nhwc, int elsize) {
-  return nhwc && elsize == 2 && bn_reduce_geom(rows, C, elsize).vec;
+template <typename F> void dispatch_act(int act, F&& f) {
+  if (act == 0) f(std::integral_constant<int, 0>{});
+  else if (act == 1) f(std::integral_constant<int, 1>{});
+  else f(std::integral_constant<int, 2>{});
+}
+template <typename F> void dispatch_bool(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
 }
 
-// finalize grid along the slabs: BN_FIN_ROWS rows per block, at most
-// BN_FIN_YMAX blocks per channel chunk
-static int64_t bn_fin_Y(int64_t S) {
-  return i64min((S + BN_FIN_ROWS - 1) / BN_FIN_ROWS, BN_FIN_YMAX);
+dim3 dim3_of(const BnGrid& g) {
+  return dim3((unsigned)g.x, (unsigned)g.y);
 }
 
-ddlb::BnWorkspacePlan ddlb::bn_workspace_plan(int64_t N, int64_t C,
-                                              int64_t HW, int nhwc,
-                                              int elsize) {
-  BnWorkspacePlan p;
-  p.S = bn_reduce_gridS(N, C, HW, nhwc, elsize);
-  p.slab_f32 = bn_slab_f32(N * HW, C, nhwc, elsize) ? 1 : 0;
-  p.slab_bytes = p.S * 2 * C * (p.slab_f32 ? 4 : 8);
+}  // namespace
+
+BnPlan ddlb::bn_plan(int64_t N, int64_t C, int64_t HW, int nhwc, int elsize,
+                     int act, int training, int masked) {
+  BnPlan p = {};
+  p.N = N; p.C = C; p.HW = HW; p.nhwc = nhwc; p.act = act;
+  const int64_t rows = N * HW, total = rows * C;
+  // the 16 B-per-lane NHWC kernels: bf16, whole 8-channel groups
+  const bool nhwc8 = nhwc && elsize == 2 && C % 8 == 0;
+  // the mask exists only where the fixed-channel apply wrote it
+  const bool use_mask = masked && act != 0 && nhwc8;
+  const BnGate gate = act == 0 ? BnGate::none
+                      : use_mask ? BnGate::mask : BnGate::y;
+
+  // stats and backward reduce
+  if (!nhwc) {
+    p.reduce = BnReduce::nchw;
+    p.reduce_grid.x = C;
+    p.reduce_grid.y = i64max(
+        i64min((rows + BN_BLOCK - 1) / BN_BLOCK,
+               i64max(BN_MAX_BLOCKS / C, 1)), 1);
+    p.reduce_gate = act == 0 ? BnGate::none : BnGate::y;
+  } else {
+    const bool vec = nhwc8 && C <= BN_VEC_REDUCE_MAX_C;
+    p.reduce = vec ? BnReduce::nhwc_vec : BnReduce::nhwc_scalar;
+    p.reduce_grid = row_grid(rows, vec ? C / 8 : C);
+    p.reduce_gate = gate;
+  }
+  p.slab_f32 = p.reduce == BnReduce::nhwc_vec;
+  p.slab_bytes = p.reduce_grid.y * 2 * C * (p.slab_f32 ? 4 : 8);
+
+  // finalize grid along the slabs: BN_FIN_ROWS rows per block, at most
+  // BN_FIN_YMAX blocks per channel chunk
+  const int64_t S = p.reduce_grid.y;
   p.cchunks = (C + BN_FIN_CH - 1) / BN_FIN_CH;
-  p.Y = bn_fin_Y(p.S);
+  p.Y = i64min((S + BN_FIN_ROWS - 1) / BN_FIN_ROWS, BN_FIN_YMAX);
   p.part_doubles = p.Y > 1 ? p.cchunks * p.Y * 2 * BN_FIN_CH : 0;
+
+  // apply and dx
+  const bool vec8ok = total % 8 == 0 && (nhwc ? C % 8 == 0 : HW % 8 == 0);
+  const BnElt stride_kind = vec8ok ? BnElt::vec : BnElt::scalar;
+  const BnGrid stride_grid = elementwise_grid(vec8ok ? total / 8 : total);
+  p.writes_mask = training && act != 0 && nhwc8;
+  const bool apply_fixed =
+      nhwc8 && (rows >= BN_FIXED_MIN_ROWS || p.writes_mask);
+  p.apply = apply_fixed ? BnElt::fixed_channel : stride_kind;
+  p.apply_grid = apply_fixed ? row_grid(rows, C / 8) : stride_grid;
+  const bool dx_fixed = nhwc8 && (rows >= BN_FIXED_MIN_ROWS || use_mask);
+  p.dx = dx_fixed ? BnElt::fixed_channel : stride_kind;
+  p.dx_grid = dx_fixed ? row_grid(rows, C / 8) : stride_grid;
+  // only the fixed-channel dx can take its gate from the mask
+  p.dx_gate = gate;
   return p;
+}
+
+// ---- launchers: each walks the plan it is given ----------------------------
+template <typename T>
+void ddlb::launch_bn_stats(const BnPlan& p, const T* x, void* sums,
+                     hipStream_t stream) {
+  const dim3 grid = dim3_of(p.reduce_grid), block(BN_BLOCK);
+  const int64_t rows = p.N * p.HW;
+  switch (p.reduce) {
+    case BnReduce::nchw:
+      hipLaunchKernelGGL((bn_reduce_nchw_kernel<StatsTerms<T, 1>>), grid,
+                         block, 0, stream, StatsTerms<T, 1>{x},
+                         (double*)sums, p.N, p.C, p.HW);
+      break;
+    case BnReduce::nhwc_scalar:
+      hipLaunchKernelGGL(
+          (bn_reduce_nhwc_kernel<1, double, true, StatsTerms<T, 1>>), grid,
+          block, 0, stream, StatsTerms<T, 1>{x}, (double*)sums, rows, p.C,
+          (int)i64min(p.C, BN_LANES));
+      break;
+    case BnReduce::nhwc_vec:
+      if constexpr (sizeof(T) == 2)
+        hipLaunchKernelGGL(
+            (bn_reduce_nhwc_kernel<8, float, false, StatsTerms<T, 8>>), grid,
+            block, 0, stream, StatsTerms<T, 8>{x}, (float*)sums, rows, p.C,
+            (int)i64min(p.C / 8, BN_LANES));
+      else
+        throw std::logic_error("bn_plan: 8-wide reduce on a 4-byte dtype");
+      break;
+  }
+  HIP_CHECK_LAST();
+}
+
+template <typename T>
+void ddlb::launch_bn_bwd_reduce(const BnPlan& p, const T* dy, const T* y,
+                          const T* x, const float* mean, const float* invstd,
+                          void* sums, const unsigned char* msk,
+                          hipStream_t stream) {
+  const dim3 grid = dim3_of(p.reduce_grid), block(BN_BLOCK);
+  const int64_t rows = p.N * p.HW;
+  dispatch_act(p.act, [&](auto A) {
+    dispatch_bool(p.reduce_gate == BnGate::mask, [&](auto M) {
+      constexpr int ACT = decltype(A)::value;
+      constexpr bool MASKED = decltype(M)::value && ACT != 0;
+      switch (p.reduce) {
+        case BnReduce::nchw: {
+          using Terms = BwdTerms<T, 1, ACT, false>;
+          hipLaunchKernelGGL((bn_reduce_nchw_kernel<Terms>), grid, block, 0,
+                             stream, Terms{dy, y, x, mean, invstd, nullptr},
+                             (double*)sums, p.N, p.C, p.HW);
+          break;
+        }
+        case BnReduce::nhwc_scalar: {
+          using Terms = BwdTerms<T, 1, ACT, MASKED>;
+          hipLaunchKernelGGL(
+              (bn_reduce_nhwc_kernel<1, double, false, Terms>), grid, block,
+              0, stream, Terms{dy, y, x, mean, invstd, msk}, (double*)sums,
+              rows, p.C, (int)i64min(p.C, BN_LANES));
+          break;
+        }
+        case BnReduce::nhwc_vec:
+          if constexpr (sizeof(T) == 2) {
+            using Terms = BwdTerms<T, 8, ACT, MASKED>;
+            hipLaunchKernelGGL(
+                (bn_reduce_nhwc_kernel<8, float, false, Terms>), grid, block,
+                0, stream, Terms{dy, y, x, mean, invstd, msk}, (float*)sums,
+                rows, p.C, (int)i64min(p.C / 8, BN_LANES));
+          } else {
+            throw std::logic_error(
+                "bn_plan: 8-wide reduce on a 4-byte dtype");
+          }
+          break;
+      }
+    });
+  });
+  HIP_CHECK_LAST();
 }
 
 // one launch for either direction; q carries the direction's pointers
 template <bool BWD>
-static void bn_finalize_launch(BnFinParams q, bool slab_f32,
-                               hipStream_t stream) {
-  const int64_t Y = bn_fin_Y(q.S);
-  q.rows_per = (int)((q.S + Y - 1) / Y);
-  const dim3 grid((unsigned)((q.C + BN_FIN_CH - 1) / BN_FIN_CH),
-                  (unsigned)Y);
+static void bn_finalize_launch(const BnPlan& p, BnFinParams q,
+                               const void* sums, double* part,
+                               unsigned* tickets, hipStream_t stream) {
+  q.sums = sums; q.part = part; q.tickets = tickets;
+  q.C = p.C; q.S = p.reduce_grid.y; q.count = (double)(p.N * p.HW);
+  q.rows_per = (int)((q.S + p.Y - 1) / p.Y);
+  const dim3 grid((unsigned)p.cchunks, (unsigned)p.Y);
   const dim3 block(BN_FIN_CH, BN_FIN_TY);
-  if (slab_f32)
+  if (p.slab_f32)
     hipLaunchKernelGGL((bn_finalize_kernel<float, BWD>), grid, block, 0,
                        stream, q);
   else
@@ -931,277 +788,129 @@ static void bn_finalize_launch(BnFinParams q, bool slab_f32,
   HIP_CHECK_LAST();
 }
 
-template <typename T>
-void ddlb::launch_bn_stats(const T* x, void* sums, int64_t N, int64_t C,
-                           int64_t HW, int64_t S, int nhwc,
-                           hipStream_t stream) {
-  const int block = 256;
-  if (nhwc) {
-    const int64_t rows = N * HW;
-    const BnGeom g = bn_reduce_geom(rows, C, (int)sizeof(T));
-    if (g.vec && sizeof(T) == 2) {
-      const int CG8 = (int)i64min(C / 8, 64);
-      hipLaunchKernelGGL((bn_stats_nhwc_vec_kernel<T>),
-                         dim3(g.cblocks, S),
-                         dim3(block), 0, stream, x, (float*)sums, rows, C,
-                         CG8);
-    } else if (g.vec && sizeof(T) == 4) {
-      const int CG4 = (int)i64min(C / 4, 64);
-      hipLaunchKernelGGL(bn_stats_nhwc_vec_f32_kernel, dim3(g.cblocks, S),
-                         dim3(block), 0, stream, (const float*)x,
-                         (double*)sums, rows, C, CG4);
-    } else {
-      const int CG = C >= 64 ? 64 : (int)C;
-      hipLaunchKernelGGL((bn_stats_nhwc_kernel<T>), dim3(g.cblocks, S),
-                         dim3(block), 0, stream, x, (double*)sums, rows, C,
-                         CG);
-    }
-  } else {
-    hipLaunchKernelGGL((bn_stats_kernel<T>), dim3(C, S), dim3(block), 0,
-                       stream, x, (double*)sums, N, C, HW);
-  }
-  HIP_CHECK_LAST();
-}
-
-void ddlb::launch_bn_finalize(const void* sums, int slab_f32, double* part,
-                              unsigned* tickets, float* mean, float* invstd,
-                              float* rm, float* rv, int64_t C, int64_t S,
-                              double count, float eps, float momentum,
-                              hipStream_t stream) {
+void ddlb::launch_bn_finalize(const BnPlan& p, const void* sums, double* part,
+                        unsigned* tickets, float* mean, float* invstd,
+                        float* rm, float* rv, float eps, float momentum,
+                        hipStream_t stream) {
   BnFinParams q = {};
-  q.sums = sums; q.part = part; q.tickets = tickets;
-  q.C = C; q.S = S; q.count = count;
   q.mean = mean; q.invstd = invstd;
   q.running_mean = rm; q.running_var = rv;
   q.eps = eps; q.momentum = momentum;
-  bn_finalize_launch<false>(q, slab_f32 != 0, stream);
+  bn_finalize_launch<false>(p, q, sums, part, tickets, stream);
 }
 
-template <typename T>
-bool ddlb::launch_bn_apply(const T* x, const T* res, T* y, const float* mean,
-                           const float* invstd, const float* gamma,
-                           const float* beta, unsigned char* msk, int64_t C,
-                           int64_t HW, int64_t total, int act, int nhwc,
-                           hipStream_t stream) {
-  const int block = 256;
-  const int64_t cdiv = nhwc ? 1 : HW;
-  const bool vec8ok = (total % 8 == 0) &&
-                      (nhwc ? (C % 8 == 0) : (HW % 8 == 0));
-  const int64_t rows_nhwc = nhwc ? total / C : 0;
-  // kernel2 starves below ~32k rows (too few blocks); grid-stride vec
-  // covers that regime — unless a mask must be written
-  if (nhwc && sizeof(T) == 2 && C % 8 == 0 && g_bn_variant != 1 &&
-      (rows_nhwc >= 32768 || (msk != nullptr && act != 0) ||
-       g_bn_variant == 2)) {
-    const int64_t rows = total / C;
-    const int CG8 = (int)i64min(C / 8, 64);
-    const int64_t cblocks = (C / 8 + CG8 - 1) / CG8;
-    int64_t S = i64min(i64max(rows / 16, 1), i64max(2048 / cblocks, 1));
-    const bool add = res != nullptr;
-#define KCASE(ACT, ADD)                                                     \
-    hipLaunchKernelGGL((bn_apply_nhwc_kernel2<T, ACT, ADD>),                \
-                       dim3(cblocks, S), dim3(block), 0, stream, x, res,    \
-                       y, mean, invstd, gamma, beta, msk, rows, C, CG8)
-    if (act == 0) { if (add) KCASE(0, true); else KCASE(0, false); }
-    else if (act == 1) { if (add) KCASE(1, true); else KCASE(1, false); }
-    else { if (add) KCASE(2, true); else KCASE(2, false); }
-#undef KCASE
-    HIP_CHECK_LAST();
-    return act != 0 && msk != nullptr;  // mask written on this path
-  }
-  if (vec8ok) {
-    const int64_t total8 = total / 8;
-    const int grid8 = elementwise_grid(total8, block);
-    const bool add = res != nullptr;
-#define VCASE(ACT, ADD, NHWC)                                               \
-    hipLaunchKernelGGL((bn_apply_vec_kernel<T, ACT, ADD, NHWC>),            \
-                       dim3(grid8), dim3(block), 0, stream, x, res, y,      \
-                       mean, invstd, gamma, beta, C, cdiv, total8)
-#define VSEL(ACT)                                                           \
-    do { if (nhwc) { if (add) VCASE(ACT, true, true);                       \
-                     else VCASE(ACT, false, true); }                        \
-         else { if (add) VCASE(ACT, true, false);                           \
-                else VCASE(ACT, false, false); } } while (0)
-    if (act == 0) VSEL(0);
-    else if (act == 1) VSEL(1);
-    else VSEL(2);
-#undef VSEL
-#undef VCASE
-    HIP_CHECK_LAST();
-    return false;
-  }
-  const int grid = elementwise_grid(total, block);
-#define CASE(ACT, ADD)                                                       \
-  hipLaunchKernelGGL((bn_apply_kernel<T, ACT, ADD>), dim3(grid), dim3(block), \
-                     0, stream, x, res, y, mean, invstd, gamma, beta, C,    \
-                     cdiv, total)
-  const bool add = res != nullptr;
-  if (act == 0 && !add) CASE(0, false);
-  else if (act == 0 && add) CASE(0, true);
-  else if (act == 1 && !add) CASE(1, false);
-  else if (act == 1 && add) CASE(1, true);
-  else if (act == 2 && !add) CASE(2, false);
-  else CASE(2, true);
-#undef CASE
-  HIP_CHECK_LAST();
-  return false;
-}
-
-template <typename T>
-void ddlb::launch_bn_bwd_reduce(const T* dy, const T* y, const T* x,
-                                const float* mean, const float* invstd,
-                                void* sums_v, const unsigned char* msk,
-                                int64_t N, int64_t C, int64_t HW, int64_t S,
-                                int act, int nhwc, hipStream_t stream) {
-  const int block = 256;
-  if (nhwc) {
-    const int64_t rows = N * HW;
-    const bool masked = msk != nullptr && act != 0;
-    const BnGeom g = bn_reduce_geom(rows, C, (int)sizeof(T));
-    if (g.vec && sizeof(T) == 2) {
-      const int CG8 = (int)i64min(C / 8, 64);
-#define CASE(ACT, MSK)                                                      \
-      hipLaunchKernelGGL((bn_bwd_reduce_nhwc_vec_kernel<T, ACT, MSK>),      \
-                         dim3(g.cblocks, S), dim3(block), 0, stream, dy,    \
-                         y, x, mean, invstd, (float*)sums_v, msk, rows, C,  \
-                         CG8)
-      if (act == 0) CASE(0, false);
-      else if (act == 1) { if (masked) CASE(1, true); else CASE(1, false); }
-      else { if (masked) CASE(2, true); else CASE(2, false); }
-#undef CASE
-    } else {
-      const int CG = C >= 64 ? 64 : (int)C;
-#define CASE(ACT, MSK)                                                      \
-      hipLaunchKernelGGL((bn_bwd_reduce_nhwc_kernel<T, ACT, MSK>),          \
-                         dim3(g.cblocks, S), dim3(block), 0, stream, dy,    \
-                         y, x, mean, invstd, (double*)sums_v, msk, rows, C, \
-                         CG)
-      if (act == 0) CASE(0, false);
-      else if (act == 1) { if (masked) CASE(1, true); else CASE(1, false); }
-      else { if (masked) CASE(2, true); else CASE(2, false); }
-#undef CASE
-    }
-  } else {
-#define CASE(ACT)                                                          \
-    hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, ACT>), dim3(C, S),         \
-                       dim3(block), 0, stream, dy, y, x, mean, invstd,     \
-                       (double*)sums_v, N, C, HW)
-    if (act == 0) CASE(0);
-    else if (act == 1) CASE(1);
-    else CASE(2);
-#undef CASE
-  }
-  HIP_CHECK_LAST();
-}
-
-void ddlb::launch_bn_bwd_finalize(const void* sums, int slab_f32,
+void ddlb::launch_bn_bwd_finalize(const BnPlan& p, const void* sums,
                                   double* part, unsigned* tickets,
                                   const float* gamma, const float* invstd,
                                   float* dgamma, float* dbeta, float* k,
-                                  int64_t C, int64_t S, double count,
                                   int training, hipStream_t stream) {
   BnFinParams q = {};
-  q.sums = sums; q.part = part; q.tickets = tickets;
-  q.C = C; q.S = S; q.count = count;
   q.gamma = gamma; q.invstd_in = invstd;
   q.dgamma = dgamma; q.dbeta = dbeta; q.k = k;
   q.training = training;
-  bn_finalize_launch<true>(q, slab_f32 != 0, stream);
+  bn_finalize_launch<true>(p, q, sums, part, tickets, stream);
 }
 
 template <typename T>
-void ddlb::launch_bn_bwd_dx(const T* dy, const T* y, const T* x,
-                            const float* mean, const float* invstd,
-                            const float* k, T* dx, T* dres,
-                            const unsigned char* msk, int64_t C, int64_t HW,
-                            int64_t total, int act, int nhwc,
+void ddlb::launch_bn_apply(const BnPlan& p, const T* x, const T* res, T* y,
+                     const float* mean, const float* invstd,
+                     const float* gamma, const float* beta,
+                     unsigned char* msk, hipStream_t stream) {
+  const dim3 grid = dim3_of(p.apply_grid), block(BN_BLOCK);
+  const int64_t rows = p.N * p.HW, total = rows * p.C;
+  const int64_t cdiv = p.nhwc ? 1 : p.HW;
+  dispatch_act(p.act, [&](auto A) {
+    dispatch_bool(res != nullptr, [&](auto R) {
+      constexpr int ACT = decltype(A)::value;
+      constexpr bool ADD = decltype(R)::value;
+      switch (p.apply) {
+        case BnElt::fixed_channel:
+          if constexpr (sizeof(T) == 2)
+            hipLaunchKernelGGL((bn_apply_fixed_kernel<ACT, ADD>), grid,
+                               block, 0, stream, x, res, y, mean, invstd,
+                               gamma, beta, p.writes_mask ? msk : nullptr,
+                               rows, p.C, (int)i64min(p.C / 8, BN_LANES));
+          else
+            throw std::logic_error(
+                "bn_plan: fixed-channel apply on a 4-byte dtype");
+          break;
+        case BnElt::vec:
+          dispatch_bool(p.nhwc != 0, [&](auto L) {
+            hipLaunchKernelGGL(
+                (bn_apply_kernel<T, 8, ACT, ADD, decltype(L)::value>), grid,
+                block, 0, stream, x, res, y, mean, invstd, gamma, beta, p.C,
+                cdiv, total / 8);
+          });
+          break;
+        case BnElt::scalar:
+          hipLaunchKernelGGL((bn_apply_kernel<T, 1, ACT, ADD, false>), grid,
+                             block, 0, stream, x, res, y, mean, invstd,
+                             gamma, beta, p.C, cdiv, total);
+          break;
+      }
+    });
+  });
+  HIP_CHECK_LAST();
+}
+
+template <typename T>
+void ddlb::launch_bn_bwd_dx(const BnPlan& p, const T* dy, const T* y,
+                            const T* x, const float* mean,
+                            const float* invstd, const float* k, T* dx,
+                            T* dres, const unsigned char* msk,
                             hipStream_t stream) {
-  const int block = 256;
-  const int64_t cdiv = nhwc ? 1 : HW;
-  const bool vec8ok = (total % 8 == 0) &&
-                      (nhwc ? (C % 8 == 0) : (HW % 8 == 0));
-  // a non-null mask FORCES the masked-capable kernel2 path (the vec
-  // fallback would read the null y)
-  const int64_t rows_nhwc = nhwc ? total / C : 0;
-  if (nhwc && sizeof(T) == 2 && C % 8 == 0 &&
-      ((g_bn_variant != 1 && rows_nhwc >= 32768) || msk != nullptr ||
-       g_bn_variant == 2)) {
-    const int64_t rows = total / C;
-    const int CG8 = (int)i64min(C / 8, 64);
-    const int64_t cblocks = (C / 8 + CG8 - 1) / CG8;
-    int64_t S = i64min(i64max(rows / 16, 1), i64max(2048 / cblocks, 1));
-    const bool add = dres != nullptr;
-    const bool masked = msk != nullptr && act != 0;
-#define KCASE(ACT, ADD, MSK)                                                \
-    hipLaunchKernelGGL((bn_bwd_dx_nhwc_kernel2<T, ACT, ADD, MSK>),          \
-                       dim3(cblocks, S), dim3(block), 0, stream, dy, y, x,  \
-                       mean, invstd, k, dx, dres, msk, rows, C, CG8)
-#define KSEL(ACT)                                                           \
-    do { if (add) { if (masked) KCASE(ACT, true, true);                     \
-                    else KCASE(ACT, true, false); }                         \
-         else { if (masked) KCASE(ACT, false, true);                        \
-                else KCASE(ACT, false, false); } } while (0)
-    if (act == 0) KSEL(0);
-    else if (act == 1) KSEL(1);
-    else KSEL(2);
-#undef KSEL
-#undef KCASE
-    HIP_CHECK_LAST();
-    return;
-  }
-  if (vec8ok) {
-    const int64_t total8 = total / 8;
-    const int grid8 = elementwise_grid(total8, block);
-    const bool add = dres != nullptr;
-#define VCASE(ACT, ADD, NHWC)                                               \
-    hipLaunchKernelGGL((bn_bwd_dx_vec_kernel<T, ACT, ADD, NHWC>),           \
-                       dim3(grid8), dim3(block), 0, stream, dy, y, x,       \
-                       mean, invstd, k, dx, dres, C, cdiv, total8)
-#define VSEL(ACT)                                                           \
-    do { if (nhwc) { if (add) VCASE(ACT, true, true);                       \
-                     else VCASE(ACT, false, true); }                        \
-         else { if (add) VCASE(ACT, true, false);                           \
-                else VCASE(ACT, false, false); } } while (0)
-    if (act == 0) VSEL(0);
-    else if (act == 1) VSEL(1);
-    else VSEL(2);
-#undef VSEL
-#undef VCASE
-    HIP_CHECK_LAST();
-    return;
-  }
-  const int grid = elementwise_grid(total, block);
-#define CASE(ACT, ADD)                                                    \
-  hipLaunchKernelGGL((bn_bwd_dx_kernel<T, ACT, ADD>), dim3(grid),         \
-                     dim3(block), 0, stream, dy, y, x, mean, invstd, k,   \
-                     dx, dres, C, cdiv, total)
-  const bool add = dres != nullptr;
-  if (act == 0 && !add) CASE(0, false);
-  else if (act == 0 && add) CASE(0, true);
-  else if (act == 1 && !add) CASE(1, false);
-  else if (act == 1 && add) CASE(1, true);
-  else if (act == 2 && !add) CASE(2, false);
-  else CASE(2, true);
-#undef CASE
+  const dim3 grid = dim3_of(p.dx_grid), block(BN_BLOCK);
+  const int64_t rows = p.N * p.HW, total = rows * p.C;
+  const int64_t cdiv = p.nhwc ? 1 : p.HW;
+  dispatch_act(p.act, [&](auto A) {
+    dispatch_bool(dres != nullptr, [&](auto R) {
+      constexpr int ACT = decltype(A)::value;
+      constexpr bool ADD = decltype(R)::value;
+      switch (p.dx) {
+        case BnElt::fixed_channel:
+          if constexpr (sizeof(T) == 2)
+            dispatch_bool(p.dx_gate == BnGate::mask, [&](auto M) {
+              constexpr bool MASKED = decltype(M)::value && ACT != 0;
+              hipLaunchKernelGGL(
+                  (bn_bwd_dx_fixed_kernel<ACT, ADD, MASKED>), grid, block, 0,
+                  stream, dy, y, x, mean, invstd, k, dx, dres, msk, rows,
+                  p.C, (int)i64min(p.C / 8, BN_LANES));
+            });
+          else
+            throw std::logic_error(
+                "bn_plan: fixed-channel dx on a 4-byte dtype");
+          break;
+        case BnElt::vec:
+          dispatch_bool(p.nhwc != 0, [&](auto L) {
+            hipLaunchKernelGGL(
+                (bn_bwd_dx_kernel<T, 8, ACT, ADD, decltype(L)::value>), grid,
+                block, 0, stream, dy, y, x, mean, invstd, k, dx, dres, p.C,
+                cdiv, total / 8);
+          });
+          break;
+        case BnElt::scalar:
+          hipLaunchKernelGGL((bn_bwd_dx_kernel<T, 1, ACT, ADD, false>), grid,
+                             block, 0, stream, dy, y, x, mean, invstd, k, dx,
+                             dres, p.C, cdiv, total);
+          break;
+      }
+    });
+  });
   HIP_CHECK_LAST();
 }
 
 #define INSTANTIATE(T)                                                        \
-  template void ddlb::launch_bn_stats<T>(                                     \
-      const T*, void*, int64_t, int64_t, int64_t, int64_t, int,             \
-      hipStream_t);                                                           \
-  template bool ddlb::launch_bn_apply<T>(                                     \
-      const T*, const T*, T*, const float*, const float*, const float*,       \
-      const float*, unsigned char*, int64_t, int64_t, int64_t, int, int,      \
-      hipStream_t);                                                           \
+  template void ddlb::launch_bn_stats<T>(const BnPlan&, const T*, void*,      \
+                                   hipStream_t);                              \
+  template void ddlb::launch_bn_apply<T>(                                     \
+      const BnPlan&, const T*, const T*, T*, const float*, const float*,      \
+      const float*, const float*, unsigned char*, hipStream_t);               \
   template void ddlb::launch_bn_bwd_reduce<T>(                                \
-      const T*, const T*, const T*, const float*, const float*, void*,        \
-      const unsigned char*, int64_t, int64_t, int64_t, int64_t, int, int,     \
-      hipStream_t);                                                           \
+      const BnPlan&, const T*, const T*, const T*, const float*,              \
+      const float*, void*, const unsigned char*, hipStream_t);                \
   template void ddlb::launch_bn_bwd_dx<T>(                                    \
-      const T*, const T*, const T*, const float*, const float*, const float*, \
-      T*, T*, const unsigned char*, int64_t, int64_t, int64_t, int, int,      \
-      hipStream_t);
+      const BnPlan&, const T*, const T*, const T*, const float*,              \
+      const float*, const float*, T*, T*, const unsigned char*, hipStream_t);
 
 INSTANTIATE(float)
 INSTANTIATE(__hip_bfloat16)

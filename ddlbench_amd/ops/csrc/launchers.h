@@ -23,51 +23,65 @@ void launch_fused_adam(uintptr_t* params, uintptr_t* grads, uintptr_t* ms,
                        int decoupled, hipStream_t stream);
 
 // ---- bn_act.hip -------------------------------------------------------
-void set_bn_variant(int v);
-int64_t bn_reduce_gridS(int64_t N, int64_t C, int64_t HW, int nhwc,
-                        int elsize);
-// Workspace of one BN reduce + finalize pair, from the same geometry
-// decision the launchers take: the reduce kernels write [S][2][C] partial
-// slabs (fp32 from the bf16 vec kernels, whose partials are fp32; double
-// from the scalar and fp32 kernels); the finalize grid is (cchunks, Y)
-// and, when Y > 1, hands double partials through part[part_doubles] and
-// one ticket word per channel chunk (zero before the first launch; the
-// kernel leaves them zero).
-struct BnWorkspacePlan {
-  int64_t S;
+// Every dispatch decision of one BN+act layer, taken once by bn_plan (pure
+// host code, no device call) and walked by the launchers below.
+enum class BnReduce { nchw, nhwc_scalar, nhwc_vec };
+enum class BnElt { fixed_channel, vec, scalar };  // apply and dx kernels
+enum class BnGate { none, y, mask };  // where backward reads the act gate
+struct BnGrid { int64_t x, y; };
+struct BnPlan {
+  int64_t N, C, HW;
+  int nhwc, act;
+  // stats and backward reduce: grid = (cblocks, S); each block writes one
+  // row of the [S][2][C] partial slabs — fp32 from the 8-wide bf16 kernels,
+  // whose partials are fp32, double from the others
+  BnReduce reduce;
+  BnGrid reduce_grid;
   int slab_f32;
   int64_t slab_bytes;
-  int64_t cchunks, Y;
-  int64_t part_doubles;
+  BnGate reduce_gate;
+  // finalize: grid = (cchunks, Y); when Y > 1 it hands double partials
+  // through part[part_doubles] and one ticket word per channel chunk (zero
+  // before the first launch; the kernel leaves them zero)
+  int64_t cchunks, Y, part_doubles;
+  // forward apply; the fixed-channel bf16 NHWC training apply also writes
+  // the 1-bit activation mask (numel/8 bytes)
+  BnElt apply;
+  BnGrid apply_grid;
+  int writes_mask;
+  // backward dx
+  BnElt dx;
+  BnGrid dx_grid;
+  BnGate dx_gate;
 };
-BnWorkspacePlan bn_workspace_plan(int64_t N, int64_t C, int64_t HW, int nhwc,
-                                  int elsize);
+// masked: the caller holds the forward's mask (honoured where a masked
+// kernel exists: act != 0, bf16 NHWC, C % 8 == 0; otherwise the gate is y)
+BnPlan bn_plan(int64_t N, int64_t C, int64_t HW, int nhwc, int elsize,
+               int act, int training, int masked);
 // sums: the slab workspace (void*: its element type follows the plan)
 template <typename T>
-void launch_bn_stats(const T*, void* sums, int64_t, int64_t, int64_t,
-                     int64_t, int, hipStream_t);
-void launch_bn_finalize(const void* sums, int slab_f32, double* part,
-                        unsigned* tickets, float*, float*, float*, float*,
-                        int64_t, int64_t, double, float, float,
-                        hipStream_t);
+void launch_bn_stats(const BnPlan&, const T* x, void* sums, hipStream_t);
+void launch_bn_finalize(const BnPlan&, const void* sums, double* part,
+                        unsigned* tickets, float* mean, float* invstd,
+                        float* running_mean, float* running_var, float eps,
+                        float momentum, hipStream_t);
 template <typename T>
-bool launch_bn_apply(const T*, const T*, T*, const float*, const float*,
-                     const float*, const float*, unsigned char*, int64_t,
-                     int64_t, int64_t, int, int, hipStream_t);
+void launch_bn_apply(const BnPlan&, const T* x, const T* res, T* y,
+                     const float* mean, const float* invstd,
+                     const float* gamma, const float* beta,
+                     unsigned char* msk, hipStream_t);
 template <typename T>
-void launch_bn_bwd_reduce(const T*, const T*, const T*, const float*,
-                          const float*, void* sums, const unsigned char*,
-                          int64_t, int64_t, int64_t, int64_t,
-                          int, int, hipStream_t);
-void launch_bn_bwd_finalize(const void* sums, int slab_f32, double* part,
-                            unsigned* tickets, const float*, const float*,
-                            float*, float*, float*, int64_t, int64_t,
-                            double, int, hipStream_t);
+void launch_bn_bwd_reduce(const BnPlan&, const T* dy, const T* y, const T* x,
+                          const float* mean, const float* invstd, void* sums,
+                          const unsigned char* msk, hipStream_t);
+void launch_bn_bwd_finalize(const BnPlan&, const void* sums, double* part,
+                            unsigned* tickets, const float* gamma,
+                            const float* invstd, float* dgamma, float* dbeta,
+                            float* k, int training, hipStream_t);
 template <typename T>
-void launch_bn_bwd_dx(const T*, const T*, const T*, const float*,
-                      const float*, const float*, T*, T*,
-                      const unsigned char*, int64_t, int64_t,
-                      int64_t, int, int, hipStream_t);
+void launch_bn_bwd_dx(const BnPlan&, const T* dy, const T* y, const T* x,
+                      const float* mean, const float* invstd, const float* k,
+                      T* dx, T* dres, const unsigned char* msk, hipStream_t);
 
 // ---- cross_entropy.hip ------------------------------------------------
 template <typename T>
