@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Fused-op microbenchmarks vs eager PyTorch: BN+ReLU(+add), CE, SGD.
+"""Fused-op microbenchmarks vs eager PyTorch: BN+ReLU(+add), CE,
+label-smoothed CE, SGD (--ops picks arms).
 
 Reports ms and achieved HBM GB/s per op over ResNet-50 activation
 shapes in both layouts — the evidence for the memory-bound fusion wins
@@ -33,19 +34,78 @@ def timeit(fn, iters, warmup):
     return (time.perf_counter() - t0) / iters
 
 
+def bench_ls_ce(dev, iters, warmup, rounds=5):
+    """Label-smoothed CE, forward + backward, bf16 logits at GNMT's vocab
+    with ~20 % of the rows ignored: the fused op against the eager
+    composition (backend="torch"), alternated in rounds in one process.
+    GB/s is taken against the byte floor: valid rows read once forward,
+    read once and written once backward = 3 * valid_rows * K * 2 bytes
+    (the zero fill of ignored dx rows is not counted)."""
+    from ddlbench_amd.ops import functional as NF
+    K = 32320
+    for R in (512, 6400):
+        g = torch.Generator(device=dev).manual_seed(R)
+        x = torch.randn(R, K, device=dev, dtype=torch.bfloat16,
+                        generator=g).requires_grad_(True)
+        t = torch.randint(1, K, (R,), device=dev, generator=g)
+        t[torch.rand(R, device=dev, generator=g) < 0.2] = 0
+        valid = int((t != 0).sum())
+
+        def step(backend):
+            x.grad = None
+            NF.label_smoothing_cross_entropy(
+                x, t, 0.1, 0, "mean", backend=backend).backward()
+
+        times = {"native": [], "torch": []}
+        peak = {}
+        for backend in times:
+            step(backend)
+            x.grad = None
+            torch.cuda.synchronize()
+            base = torch.cuda.memory_allocated()
+            torch.cuda.reset_peak_memory_stats()
+            step(backend)
+            torch.cuda.synchronize()
+            # beyond the logits: dx included, it is part of either arm
+            peak[backend] = torch.cuda.max_memory_allocated() - base
+        for _ in range(rounds):
+            for backend in times:
+                times[backend].append(
+                    timeit(lambda: step(backend), iters, warmup))
+        med = {b: sorted(v)[len(v) // 2] for b, v in times.items()}
+        floor = 3 * valid * K * 2
+        print(json.dumps({
+            "op": "ls_ce_fwd_bwd", "shape": f"{R}x{K}", "dtype": "bfloat16",
+            "valid_rows": valid,
+            "fused_ms": round(med["native"] * 1e3, 4),
+            "fused_ms_min": round(min(times["native"]) * 1e3, 4),
+            "eager_ms": round(med["torch"] * 1e3, 4),
+            "eager_ms_min": round(min(times["torch"]) * 1e3, 4),
+            "speedup": round(med["torch"] / med["native"], 2),
+            "fused_GBs": round(floor / med["native"] / 1e9, 0),
+            "floor_bytes": floor,
+            "fused_peak_MB": round(peak["native"] / 2**20, 1),
+            "eager_peak_MB": round(peak["torch"] / 2**20, 1)}), flush=True)
+        del x, t
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--iters", type=int, default=20)
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--dtype", default="bfloat16")
+    p.add_argument("--ops", default="bn,ce,ls_ce,sgd",
+                   help="comma-separated arms: bn, ce, ls_ce, sgd")
     args = p.parse_args()
+    arms = set(args.ops.split(","))
+    assert arms <= {"bn", "ce", "ls_ce", "sgd"}, args.ops
     assert torch.cuda.is_available()
     from ddlbench_amd.ops import functional as NF
     dev = torch.device("cuda", 0)
     dt = torch.bfloat16 if args.dtype == "bfloat16" else torch.float32
     esz = torch.tensor([], dtype=dt).element_size()
 
-    for nhwc in (False, True):
+    for nhwc in ((False, True) if "bn" in arms else ()):
         fmt = torch.channels_last if nhwc else torch.contiguous_format
         for N, C, H, W in SHAPES:
             x = torch.randn(N, C, H, W, device=dev, dtype=dt) \
@@ -115,7 +175,8 @@ def main():
             print(json.dumps(row), flush=True)
 
     # cross entropy
-    for B, K in [(256, 1000), (512, 1000), (512, 32320)]:
+    for B, K in ([(256, 1000), (512, 1000), (512, 32320)]
+                 if "ce" in arms else []):
         logits = torch.randn(B, K, device=dev, dtype=dt,
                              requires_grad=True)
         tgt = torch.randint(K, (B,), device=dev)
@@ -130,6 +191,11 @@ def main():
                           "eager_ms": round(t_e * 1e3, 4),
                           "speedup": round(t_e / t_f, 2)}), flush=True)
 
+    if "ls_ce" in arms:
+        bench_ls_ce(dev, args.iters, args.warmup)
+
+    if "sgd" not in arms:
+        return
     # fused SGD on resnet50-sized param set
     from ddlbench_amd.models import build_model
     from ddlbench_amd.ops.sgd import FusedSGD

@@ -19,6 +19,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ddlbench_amd import ops as _ops
+from ddlbench_amd.ops import functional as NF
 
 PAD, BOS, EOS = 0, 1, 2
 
@@ -355,20 +356,16 @@ class LabelSmoothingLoss(nn.Module):
     """Per-token label-smoothed CE ignoring PAD
     (reference train/smoothing.py:7-18)."""
 
-    def __init__(self, smoothing: float = 0.1, padding_idx: int = PAD):
+    def __init__(self, smoothing: float = 0.1, padding_idx: int = PAD,
+                 backend: str = "auto"):
         super().__init__()
         self.smoothing = smoothing
         self.padding_idx = padding_idx
+        self.backend = backend
 
     def forward(self, logits, target):
-        # logits: (T, B, V); target: (T, B)
-        V = logits.size(-1)
-        logits = logits.reshape(-1, V).float()
-        target = target.reshape(-1)
-        non_pad = target != self.padding_idx
-        logp = F.log_softmax(logits, dim=-1)
-        nll = -logp.gather(1, target.clamp_min(0).unsqueeze(1)).squeeze(1)
-        smooth = -logp.mean(dim=-1)
-        loss = (1 - self.smoothing) * nll + self.smoothing * smooth
-        n_tokens = non_pad.sum().clamp_min(1)
-        return (loss * non_pad).sum() / n_tokens
+        # logits: (T, B, V); target: (T, B). Native kernels on a GPU, the
+        # torch composition on CPU (ops.use_native).
+        return NF.label_smoothing_cross_entropy(
+            logits, target, self.smoothing, ignore_index=self.padding_idx,
+            reduction="mean", backend=self.backend)

@@ -353,6 +353,77 @@ torch::Tensor ce_bwd(torch::Tensor logits, torch::Tensor target,
   return dx;
 }
 
+// ---- label-smoothed cross entropy with an ignore index -----------------
+void check_ls_ce(const torch::Tensor& logits, const torch::Tensor& target) {
+  check_gpu_contig(logits, "logits");
+  check_gpu_contig(target, "target");
+  TORCH_CHECK(logits.dim() == 2, "ls_ce: logits must be (R, K)");
+  TORCH_CHECK(logits.scalar_type() == at::kFloat || is_bf16(logits),
+              "ls_ce: logits must be fp32 or bf16");
+  TORCH_CHECK(target.scalar_type() == at::kLong,
+              "ls_ce: target must be int64");
+  TORCH_CHECK(target.device() == logits.device(),
+              "ls_ce: target must be on the logits' device");
+  TORCH_CHECK(target.dim() == 1 && target.size(0) == logits.size(0),
+              "ls_ce: target must be (R,)");
+  TORCH_CHECK(logits.size(1) >= 1 && logits.size(1) < (1LL << 30),
+              "ls_ce: K must be in [1, 2^30)");
+  TORCH_CHECK(logits.size(0) < (1LL << 31), "ls_ce: too many rows");
+}
+
+// -> {loss (0-dim fp32), lse[R], n_valid (0-dim int64)}
+std::vector<torch::Tensor> ls_ce_fwd(torch::Tensor logits,
+                                     torch::Tensor target, double smoothing,
+                                     int64_t ignore_index, bool mean) {
+  check_ls_ce(logits, target);
+  const int64_t R = logits.size(0), K = logits.size(1);
+  auto s = cur_stream();
+  auto fopt = logits.options().dtype(at::kFloat);
+  // row 0: lse (returned), row 1: per-row losses (every slot written)
+  torch::Tensor rows = torch::empty({2, R}, fopt);
+  torch::Tensor loss = torch::empty({}, fopt);
+  torch::Tensor n_valid = torch::empty({}, fopt.dtype(at::kLong));
+  dispatch_f32_bf16(logits, [&](auto tag) {
+    using T = decltype(tag);
+    launch_ls_ce_fwd<T>(dptr<T>(logits), dptr<int64_t>(target),
+                        dptr<float>(rows) + R, dptr<float>(rows),
+                        dptr<float>(loss), dptr<int64_t>(n_valid), R, K,
+                        (float)smoothing, ignore_index, mean, s);
+  });
+  return {loss, rows[0], n_valid};
+}
+
+torch::Tensor ls_ce_bwd(torch::Tensor logits, torch::Tensor target,
+                        torch::Tensor lse, torch::Tensor n_valid,
+                        torch::Tensor grad_out, double smoothing,
+                        int64_t ignore_index, bool mean) {
+  check_ls_ce(logits, target);
+  check_gpu_contig(lse, "lse");
+  check_gpu_contig(n_valid, "n_valid");
+  check_gpu_contig(grad_out, "grad_out");
+  const int64_t R = logits.size(0), K = logits.size(1);
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.numel() == R,
+              "ls_ce_bwd: lse must be fp32 (R,)");
+  TORCH_CHECK(n_valid.scalar_type() == at::kLong && n_valid.numel() == 1,
+              "ls_ce_bwd: n_valid must be one int64");
+  TORCH_CHECK(grad_out.scalar_type() == at::kFloat && grad_out.numel() == 1,
+              "ls_ce_bwd: grad_out must be one fp32");
+  TORCH_CHECK(lse.device() == logits.device() &&
+                  n_valid.device() == logits.device() &&
+                  grad_out.device() == logits.device(),
+              "ls_ce_bwd: all tensors must be on the logits' device");
+  auto s = cur_stream();
+  torch::Tensor dx = torch::empty_like(logits);
+  dispatch_f32_bf16(logits, [&](auto tag) {
+    using T = decltype(tag);
+    launch_ls_ce_bwd<T>(dptr<T>(logits), dptr<int64_t>(target),
+                        dptr<float>(lse), dptr<int64_t>(n_valid),
+                        dptr<float>(grad_out), dptr<T>(dx), R, K,
+                        (float)smoothing, ignore_index, mean, s);
+  });
+  return dx;
+}
+
 // ---- MFMA implicit-GEMM conv (NHWC bf16) ------------------------------
 // x: (N,C,H,W) logical, channels_last memory; w: (K,C,R,S) logical,
 // channels_last memory (= (K,R,S,C) image). Returns channels_last y.
@@ -785,6 +856,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "NHWC bf16 MFMA stem conv (C < 8) weight-grad (fp32 out)");
   m.def("ce_fwd", &ce_fwd, "cross-entropy forward");
   m.def("ce_bwd", &ce_bwd, "cross-entropy backward");
+  m.def("ls_ce_fwd", &ls_ce_fwd,
+        "label-smoothed cross-entropy forward (ignore index)");
+  m.def("ls_ce_bwd", &ls_ce_bwd, "label-smoothed cross-entropy backward");
   m.def("revert_varlen", &revert_varlen,
         "reverse each batch element's valid time prefix (T,B,F)");
   m.def("varlen_mask", &varlen_mask, "valid-timestep mask (T,B) uint8");

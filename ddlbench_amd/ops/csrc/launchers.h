@@ -90,6 +90,21 @@ void launch_ce_fwd(const T*, const int64_t*, float*, float*, int64_t,
 template <typename T>
 void launch_ce_bwd(const T*, const int64_t*, const float*, const float*, T*,
                    int64_t, int64_t, hipStream_t);
+// Label-smoothed CE with an ignore index. Forward writes loss_r[R] and
+// lse[R] per row, then loss[0] (mean over non-ignored rows, count clamped
+// to 1, or the plain sum) and n_valid[0]; backward forms its scale from
+// grad_out[0] and n_valid[0] on the device. K < 2^30.
+template <typename T>
+void launch_ls_ce_fwd(const T* logits, const int64_t* target, float* loss_r,
+                      float* lse, float* loss, int64_t* n_valid, int64_t R,
+                      int64_t K, float smoothing, int64_t ignore_index,
+                      int mean, hipStream_t);
+template <typename T>
+void launch_ls_ce_bwd(const T* logits, const int64_t* target,
+                      const float* lse, const int64_t* n_valid,
+                      const float* grad_out, T* dx, int64_t R, int64_t K,
+                      float smoothing, int64_t ignore_index, int mean,
+                      hipStream_t);
 
 // ---- conv_mfma.hip: forward (dgrad=0) or data-grad (dgrad=1); the dims
 // are always those of the forward conv. add (dgrad only, nullptr = none)

@@ -120,6 +120,70 @@ def cross_entropy(logits: torch.Tensor, target: torch.Tensor,
     return F.cross_entropy(logits, target)
 
 
+# ---------------------------------------- label-smoothed cross entropy
+class _FusedLSCrossEntropy(torch.autograd.Function):
+    """Everything stays on the device: the valid-token count the backward
+    scale needs is a saved tensor the kernel reads, never a host value."""
+
+    @staticmethod
+    def forward(ctx, logits, target, smoothing, ignore_index, mean):
+        ext = _ops.require_extension()
+        loss, lse, n_valid = ext.ls_ce_fwd(logits, target, smoothing,
+                                           ignore_index, mean)
+        ctx.save_for_backward(logits, target, lse, n_valid)
+        ctx.cfg = (smoothing, ignore_index, mean)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        ext = _ops.require_extension()
+        logits, target, lse, n_valid = ctx.saved_tensors
+        g = grad_out.detach().float().contiguous()
+        dx = ext.ls_ce_bwd(logits, target, lse, n_valid, g, *ctx.cfg)
+        return dx, None, None, None, None
+
+
+def label_smoothing_cross_entropy(logits: torch.Tensor, target: torch.Tensor,
+                                  smoothing: float = 0.1,
+                                  ignore_index: int = -100,
+                                  reduction: str = "mean",
+                                  backend: str = "auto") -> torch.Tensor:
+    """Per-token label-smoothed cross-entropy over (..., K) logits and
+    (...) int64 targets; tokens equal to ``ignore_index`` contribute
+    nothing. ``reduction="mean"`` divides by the number of non-ignored
+    tokens clamped to 1 (all ignored -> 0, not NaN); ``"sum"`` does not
+    divide. Returns an fp32 scalar for fp32 / bf16 logits."""
+    if reduction not in ("mean", "sum"):
+        raise ValueError(f"reduction must be 'mean' or 'sum', got "
+                         f"{reduction!r}")
+    K = logits.size(-1)
+    logits = logits.reshape(-1, K)
+    target = target.reshape(-1)
+    mean = reduction == "mean"
+    if _ops.use_native(logits, backend):
+        logits = logits.contiguous()
+        target = target.contiguous()
+        if torch.is_grad_enabled() and logits.requires_grad:
+            return _FusedLSCrossEntropy.apply(
+                logits, target, float(smoothing), int(ignore_index), mean)
+        # nothing to differentiate: keep neither the logits nor lse
+        return _ops.require_extension().ls_ce_fwd(
+            logits.detach(), target, float(smoothing), int(ignore_index),
+            mean)[0]
+    if logits.dtype != torch.float64:
+        logits = logits.float()
+    non_pad = target != ignore_index
+    logp = F.log_softmax(logits, dim=-1)
+    nll = -logp.gather(1, target.clamp_min(0).unsqueeze(1)).squeeze(1)
+    smooth = -logp.mean(dim=-1)
+    loss = (1 - smoothing) * nll + smoothing * smooth
+    total = (loss * non_pad).sum()
+    if not mean:
+        return total
+    n_tokens = non_pad.sum().clamp_min(1)
+    return total / n_tokens
+
+
 # ------------------------------------------------------- depthwise conv3x3
 class _FusedDWConv3x3(torch.autograd.Function):
     @staticmethod

@@ -112,3 +112,28 @@ class CrossEntropyLoss(nn.Module):
     def forward(self, logits: torch.Tensor,
                 target: torch.Tensor) -> torch.Tensor:
         return NF.cross_entropy(logits, target, backend=_DEFAULT_BACKEND)
+
+
+class LabelSmoothingCrossEntropy(nn.Module):
+    """Fused label-smoothed cross-entropy over (..., K) logits; targets
+    equal to ``ignore_index`` are skipped. ``reduction`` is "mean" (over
+    the non-ignored tokens, count clamped to 1) or "sum"."""
+
+    def __init__(self, smoothing: float = 0.1, ignore_index: int = -100,
+                 reduction: str = "mean"):
+        super().__init__()
+        assert reduction in ("mean", "sum")
+        self.smoothing = smoothing
+        self.ignore_index = ignore_index
+        self.reduction = reduction
+
+    def forward(self, logits: torch.Tensor,
+                target: torch.Tensor) -> torch.Tensor:
+        return NF.label_smoothing_cross_entropy(
+            logits, target, self.smoothing, self.ignore_index,
+            self.reduction, backend=_DEFAULT_BACKEND)
+
+    def extra_repr(self) -> str:
+        return (f"smoothing={self.smoothing}, "
+                f"ignore_index={self.ignore_index}, "
+                f"reduction={self.reduction}")
