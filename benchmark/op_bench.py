@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Fused-op microbenchmarks vs eager PyTorch: BN+ReLU(+add), CE,
-label-smoothed CE, SGD (--ops picks arms).
+label-smoothed CE, attention score, SGD (--ops picks arms).
 
 Reports ms and achieved HBM GB/s per op over ResNet-50 activation
 shapes in both layouts — the evidence for the memory-bound fusion wins
@@ -89,16 +89,87 @@ def bench_ls_ce(dev, iters, warmup, rounds=5):
         del x, t
 
 
+def bench_attn(dev, iters, warmup, rounds=5):
+    """Bahdanau attention score, bf16, H = 1024, about a fifth of the keys
+    masked through per-sentence lengths: the fused op against the eager
+    composition (backend="torch"), alternated in rounds in one process.
+    Training shapes run forward + backward through autograd, the decode
+    shape (Tq = 1) forward only under no_grad. Gtanh/s is
+    valid (b,i,j) * H over the fused time: the size of the problem, not the
+    kernels' own evaluation count (a training step evaluates tanh three
+    times per element: once forward, twice in the two backward sweeps)."""
+    from ddlbench_amd.ops import functional as NF
+    H = 1024
+    dt = torch.bfloat16
+    for B, Tq, Tk, train in ((64, 32, 32, True), (128, 50, 50, True),
+                             (64, 1, 50, False)):
+        g = torch.Generator(device=dev).manual_seed(B * Tk)
+        mk = lambda *s: torch.randn(*s, device=dev, dtype=dt, generator=g)
+        q, k = mk(B, Tq, H), mk(B, Tk, H)
+        bias = 0.1 * mk(H)
+        vn = mk(H)
+        vn = vn / vn.float().norm().to(dt)
+        ds = mk(B, Tq, Tk)
+        # lengths in [0.6 Tk, Tk]: a fifth of the keys masked on average
+        lengths = (Tk * (0.6 + 0.4 * torch.rand(B, device=dev, generator=g))
+                   ).round().long().clamp(1, Tk)
+        mask = torch.arange(Tk, device=dev).unsqueeze(0) \
+            < lengths.unsqueeze(1)
+        valid = int(mask.sum()) * Tq
+        leaves = [t.requires_grad_(train) for t in (q, k, bias, vn)]
+
+        def step(backend):
+            if not train:
+                with torch.no_grad():
+                    NF.attention_score(*leaves, mask, backend=backend)
+                return
+            for t in leaves:
+                t.grad = None
+            NF.attention_score(*leaves, mask, backend=backend).backward(ds)
+
+        times = {"native": [], "torch": []}
+        peak = {}
+        for backend in times:
+            step(backend)
+            for t in leaves:
+                t.grad = None
+            torch.cuda.synchronize()
+            base = torch.cuda.memory_allocated()
+            torch.cuda.reset_peak_memory_stats()
+            step(backend)
+            torch.cuda.synchronize()
+            # beyond the inputs: outputs and gradients are part of each arm
+            peak[backend] = torch.cuda.max_memory_allocated() - base
+        for _ in range(rounds):
+            for backend in times:
+                times[backend].append(
+                    timeit(lambda: step(backend), iters, warmup))
+        med = {b: sorted(v)[len(v) // 2] for b, v in times.items()}
+        print(json.dumps({
+            "op": "attn_score_fwd_bwd" if train else "attn_score_fwd",
+            "shape": f"B{B} Tq{Tq} Tk{Tk} H{H}", "dtype": "bfloat16",
+            "valid_bij": valid,
+            "fused_ms": round(med["native"] * 1e3, 4),
+            "fused_ms_min": round(min(times["native"]) * 1e3, 4),
+            "eager_ms": round(med["torch"] * 1e3, 4),
+            "eager_ms_min": round(min(times["torch"]) * 1e3, 4),
+            "speedup": round(med["torch"] / med["native"], 2),
+            "fused_Gtanh_s": round(valid * H / med["native"] / 1e9, 1),
+            "fused_peak_MB": round(peak["native"] / 2**20, 2),
+            "eager_peak_MB": round(peak["torch"] / 2**20, 2)}), flush=True)
+        del q, k, ds, leaves
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--iters", type=int, default=20)
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--dtype", default="bfloat16")
-    p.add_argument("--ops", default="bn,ce,ls_ce,sgd",
-                   help="comma-separated arms: bn, ce, ls_ce, sgd")
+    p.add_argument("--ops", default="bn,ce,ls_ce,attn,sgd",
+                   help="comma-separated arms: bn, ce, ls_ce, attn, sgd")
     args = p.parse_args()
     arms = set(args.ops.split(","))
-    assert arms <= {"bn", "ce", "ls_ce", "sgd"}, args.ops
+    assert arms <= {"bn", "ce", "ls_ce", "attn", "sgd"}, args.ops
     assert torch.cuda.is_available()
     from ddlbench_amd.ops import functional as NF
     dev = torch.device("cuda", 0)
@@ -193,6 +264,9 @@ def main():
 
     if "ls_ce" in arms:
         bench_ls_ce(dev, args.iters, args.warmup)
+
+    if "attn" in arms:
+        bench_attn(dev, args.iters, args.warmup)
 
     if "sgd" not in arms:
         return

@@ -12,6 +12,7 @@ HIP kernel (ops/csrc/seq_utils.hip) with a torch fallback on CPU."""
 from __future__ import annotations
 
 import math
+import os
 from typing import Optional
 
 import torch
@@ -116,9 +117,13 @@ class ResidualRecurrentEncoder(nn.Module):
 
 # ------------------------------------------------------------ attention
 class BahdanauAttention(nn.Module):
-    """Normalized additive attention (reference attention.py:12-115)."""
+    """Normalized additive attention (reference attention.py:12-115).
+    The score runs the fused native kernels on a GPU and the torch
+    composition on CPU; ``backend`` ("auto", "native", "torch") or, while it
+    is "auto", DDLB_ATTN_SCORE picks one explicitly."""
 
-    def __init__(self, query_size: int, key_size: int, hidden: int):
+    def __init__(self, query_size: int, key_size: int, hidden: int,
+                 backend: str = "auto"):
         super().__init__()
         self.linear_q = nn.Linear(query_size, hidden, bias=False)
         self.linear_k = nn.Linear(key_size, hidden, bias=False)
@@ -127,20 +132,30 @@ class BahdanauAttention(nn.Module):
         self.g = nn.Parameter(torch.tensor(math.sqrt(1.0 / hidden)))
         nn.init.uniform_(self.v, -1.0 / math.sqrt(hidden),
                          1.0 / math.sqrt(hidden))
+        self.backend = backend
 
-    def score(self, q, k):
-        # q: (B, Tq, H'), k: (B, Tk, H')
+    def resolve_backend(self) -> str:
+        """The backend the next forward uses; the environment is read here,
+        per call, and only while the module's own setting is "auto"."""
+        backend = self.backend
+        if backend == "auto":
+            backend = os.environ.get("DDLB_ATTN_SCORE", "auto")
+        if backend not in ("auto", "native", "torch"):
+            raise ValueError("attention score backend must be auto, native "
+                             f"or torch, got {backend!r}")
+        return backend
+
+    def score(self, q, k, mask: Optional[torch.Tensor] = None):
+        # q: (B, Tq, H'), k: (B, Tk, H'); masked keys score -65504
         vn = self.g * self.v / self.v.norm()
-        s = torch.tanh(q.unsqueeze(2) + k.unsqueeze(1) + self.b)
-        return torch.einsum("bqkh,h->bqk", s, vn)
+        return NF.attention_score(q, k, self.b, vn, mask,
+                                  self.resolve_backend())
 
     def forward(self, query, keys, mask: Optional[torch.Tensor] = None):
         # query: (B, Tq, Hq); keys: (B, Tk, Hk); mask: (B, Tk) bool valid
         q = self.linear_q(query)
         k = self.linear_k(keys)
-        scores = self.score(q, k)
-        if mask is not None:
-            scores = scores.masked_fill(~mask.unsqueeze(1), -65504.0)
+        scores = self.score(q, k, mask)
         attn = F.softmax(scores.float(), dim=-1).to(keys.dtype)
         ctx = torch.bmm(attn, keys)
         return ctx, attn

@@ -424,6 +424,112 @@ torch::Tensor ls_ce_bwd(torch::Tensor logits, torch::Tensor target,
   return dx;
 }
 
+// ---- fused Bahdanau attention score ------------------------------------
+// Returns the mask's data pointer (nullptr without a mask).
+const uint8_t* check_attn_score(const torch::Tensor& q,
+                                const torch::Tensor& k,
+                                const torch::Tensor& bias,
+                                const torch::Tensor& vn,
+                                const c10::optional<torch::Tensor>& mask) {
+  check_gpu_contig(q, "q");
+  check_gpu_contig(k, "k");
+  check_gpu_contig(bias, "bias");
+  check_gpu_contig(vn, "vn");
+  TORCH_CHECK(q.scalar_type() == at::kFloat || is_bf16(q),
+              "attn_score: q must be fp32 or bf16");
+  TORCH_CHECK(k.scalar_type() == q.scalar_type() &&
+                  bias.scalar_type() == q.scalar_type() &&
+                  vn.scalar_type() == q.scalar_type(),
+              "attn_score: q, k, bias and vn must share one dtype");
+  TORCH_CHECK(k.device() == q.device() && bias.device() == q.device() &&
+                  vn.device() == q.device(),
+              "attn_score: all tensors must be on q's device");
+  TORCH_CHECK(q.dim() == 3, "attn_score: q must be (B, Tq, H)");
+  TORCH_CHECK(k.dim() == 3 && k.size(0) == q.size(0) &&
+                  k.size(2) == q.size(2),
+              "attn_score: k must be (B, Tk, H) with q's B and H");
+  const int64_t B = q.size(0), H = q.size(2);
+  TORCH_CHECK(H >= 1, "attn_score: H must be at least 1");
+  TORCH_CHECK(bias.dim() == 1 && bias.size(0) == H,
+              "attn_score: bias must be (H,) with q's H");
+  TORCH_CHECK(vn.dim() == 1 && vn.size(0) == H,
+              "attn_score: vn must be (H,) with q's H");
+  TORCH_CHECK(B * ((H + 63) / 64) < (1LL << 31),
+              "attn_score: B * ceil(H / 64) must be below 2^31");
+  if (!mask.has_value()) return nullptr;
+  const torch::Tensor& m = *mask;
+  check_gpu_contig(m, "mask");
+  TORCH_CHECK(m.scalar_type() == at::kBool || m.scalar_type() == at::kByte,
+              "attn_score: mask must be bool or uint8");
+  TORCH_CHECK(m.device() == q.device(),
+              "attn_score: mask must be on q's device");
+  TORCH_CHECK(m.dim() == 2 && m.size(0) == B && m.size(1) == k.size(1),
+              "attn_score: mask must be (B, Tk)");
+  return reinterpret_cast<const uint8_t*>(m.data_ptr());
+}
+
+torch::Tensor attn_score_fwd(torch::Tensor q, torch::Tensor k,
+                             torch::Tensor bias, torch::Tensor vn,
+                             c10::optional<torch::Tensor> mask) {
+  const uint8_t* mp = check_attn_score(q, k, bias, vn, mask);
+  const int64_t B = q.size(0), Tq = q.size(1), Tk = k.size(1), H = q.size(2);
+  torch::Tensor out = torch::empty({B, Tq, Tk}, q.options());
+  auto s = cur_stream();
+  dispatch_f32_bf16(q, [&](auto tag) {
+    using T = decltype(tag);
+    launch_attn_score_fwd<T>(dptr<T>(q), dptr<T>(k), dptr<T>(bias),
+                             dptr<T>(vn), mp, dptr<T>(out), B, Tq, Tk, H, s);
+  });
+  return out;
+}
+
+// -> {dq, dk, dbias, dvn}; need_q covers dq, dbias and dvn (one sweep makes
+// all three), need_k covers dk. What is not needed comes back undefined.
+std::vector<torch::Tensor> attn_score_bwd(torch::Tensor ds, torch::Tensor q,
+                                          torch::Tensor k, torch::Tensor bias,
+                                          torch::Tensor vn,
+                                          c10::optional<torch::Tensor> mask,
+                                          bool need_q, bool need_k) {
+  const uint8_t* mp = check_attn_score(q, k, bias, vn, mask);
+  check_gpu_contig(ds, "ds");
+  const int64_t B = q.size(0), Tq = q.size(1), Tk = k.size(1), H = q.size(2);
+  TORCH_CHECK(ds.scalar_type() == q.scalar_type() &&
+                  ds.device() == q.device(),
+              "attn_score_bwd: ds must have q's dtype and device");
+  TORCH_CHECK(ds.dim() == 3 && ds.size(0) == B && ds.size(1) == Tq &&
+                  ds.size(2) == Tk,
+              "attn_score_bwd: ds must be (B, Tq, Tk)");
+  torch::Tensor dq, dk, dbias, dvn, slab;
+  if (need_q) {
+    dq = torch::empty_like(q);
+    dbias = torch::empty_like(bias);
+    dvn = torch::empty_like(vn);
+    slab = torch::empty({2, B, H}, q.options().dtype(at::kFloat));
+    if (B == 0 || Tq == 0 || Tk == 0) {  // the kernels do not run
+      dq.zero_();
+      dbias.zero_();
+      dvn.zero_();
+    }
+  }
+  if (need_k) {
+    dk = torch::empty_like(k);
+    if (B == 0 || Tq == 0 || Tk == 0) dk.zero_();
+  }
+  auto s = cur_stream();
+  dispatch_f32_bf16(q, [&](auto tag) {
+    using T = decltype(tag);
+    auto p = [](const torch::Tensor& t) {
+      return t.defined() ? dptr<T>(t) : nullptr;
+    };
+    launch_attn_score_bwd<T>(
+        dptr<T>(ds), dptr<T>(q), dptr<T>(k), dptr<T>(bias), dptr<T>(vn), mp,
+        p(dq), p(dk), p(dbias), p(dvn),
+        slab.defined() ? dptr<float>(slab) : nullptr, B, Tq, Tk, H, need_q,
+        need_k, s);
+  });
+  return {dq, dk, dbias, dvn};
+}
+
 // ---- MFMA implicit-GEMM conv (NHWC bf16) ------------------------------
 // x: (N,C,H,W) logical, channels_last memory; w: (K,C,R,S) logical,
 // channels_last memory (= (K,R,S,C) image). Returns channels_last y.
@@ -859,6 +965,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ls_ce_fwd", &ls_ce_fwd,
         "label-smoothed cross-entropy forward (ignore index)");
   m.def("ls_ce_bwd", &ls_ce_bwd, "label-smoothed cross-entropy backward");
+  m.def("attn_score_fwd", &attn_score_fwd,
+        "fused Bahdanau attention score forward (B,Tq,Tk)", py::arg("q"),
+        py::arg("k"), py::arg("bias"), py::arg("vn"),
+        py::arg("mask") = py::none());
+  m.def("attn_score_bwd", &attn_score_bwd,
+        "fused Bahdanau attention score backward -> dq, dk, dbias, dvn",
+        py::arg("ds"), py::arg("q"), py::arg("k"), py::arg("bias"),
+        py::arg("vn"), py::arg("mask") = py::none(),
+        py::arg("need_q") = true, py::arg("need_k") = true);
   m.def("revert_varlen", &revert_varlen,
         "reverse each batch element's valid time prefix (T,B,F)");
   m.def("varlen_mask", &varlen_mask, "valid-timestep mask (T,B) uint8");

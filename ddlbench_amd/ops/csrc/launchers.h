@@ -106,6 +106,24 @@ void launch_ls_ce_bwd(const T* logits, const int64_t* target,
                       float smoothing, int64_t ignore_index, int mean,
                       hipStream_t);
 
+// ---- attn_score.hip ---------------------------------------------------
+// scores[b,i,j] = sum_h vn[h] * tanh(q[b,i,h] + k[b,j,h] + bias[h]) for
+// q (B,Tq,H), k (B,Tk,H); mask (B,Tk), 1 = valid key, nullptr = none. A
+// masked key scores -65504 and is never read. B * ceil(H / 64) < 2^31.
+template <typename T>
+void launch_attn_score_fwd(const T* q, const T* k, const T* bias,
+                           const T* vn, const uint8_t* mask, T* scores,
+                           int64_t B, int64_t Tq, int64_t Tk, int64_t H,
+                           hipStream_t);
+// need_q: dq, dbias and dvn are written (slab: 2*B*H floats of workspace);
+// need_k: dk is written. Pointers of a part that is not needed stay unused.
+template <typename T>
+void launch_attn_score_bwd(const T* ds, const T* q, const T* k,
+                           const T* bias, const T* vn, const uint8_t* mask,
+                           T* dq, T* dk, T* dbias, T* dvn, float* slab,
+                           int64_t B, int64_t Tq, int64_t Tk, int64_t H,
+                           int need_q, int need_k, hipStream_t);
+
 // ---- conv_mfma.hip: forward (dgrad=0) or data-grad (dgrad=1); the dims
 // are always those of the forward conv. add (dgrad only, nullptr = none)
 // is a read-only bf16 tensor of dx's geometry summed into dx in the

@@ -184,6 +184,59 @@ def label_smoothing_cross_entropy(logits: torch.Tensor, target: torch.Tensor,
     return total / n_tokens
 
 
+# ------------------------------------------- Bahdanau attention score
+MASKED_SCORE = -65504.0
+
+
+class _FusedAttnScore(torch.autograd.Function):
+    """Saves only the inputs: backward recomputes tanh, so the
+    (B, Tq, Tk, H) tensor of the eager composition never exists."""
+
+    @staticmethod
+    def forward(ctx, q, k, bias, vn, mask):
+        ext = _ops.require_extension()
+        ctx.save_for_backward(q, k, bias, vn, mask)
+        return ext.attn_score_fwd(q, k, bias, vn, mask)
+
+    @staticmethod
+    def backward(ctx, ds):
+        ext = _ops.require_extension()
+        q, k, bias, vn, mask = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        # one sweep over the q rows makes dq, dbias and dvn together
+        need_q, need_k = need[0] or need[2] or need[3], need[1]
+        dq, dk, dbias, dvn = ext.attn_score_bwd(
+            ds.contiguous(), q, k, bias, vn, mask, need_q, need_k)
+        return (dq if need[0] else None, dk, dbias if need[2] else None,
+                dvn if need[3] else None, None)
+
+
+def attention_score(q: torch.Tensor, k: torch.Tensor, bias: torch.Tensor,
+                    vn: torch.Tensor, mask: Optional[torch.Tensor] = None,
+                    backend: str = "auto") -> torch.Tensor:
+    """Additive attention scores ``sum_h vn[h] * tanh(q[b,i,h] + k[b,j,h]
+    + bias[h])`` for q (B, Tq, H) and k (B, Tk, H), as (B, Tq, Tk) in the
+    inputs' dtype. ``mask`` is (B, Tk) bool, True for a valid key; a masked
+    key scores ``MASKED_SCORE`` and takes no gradient."""
+    if _ops.use_native(q, backend):
+        q, k = q.contiguous(), k.contiguous()
+        bias, vn = bias.contiguous(), vn.contiguous()
+        if mask is not None:
+            mask = mask.contiguous()
+        if torch.is_grad_enabled() and (
+                q.requires_grad or k.requires_grad or bias.requires_grad
+                or vn.requires_grad):
+            return _FusedAttnScore.apply(q, k, bias, vn, mask)
+        # nothing to differentiate (beam search, Tq = 1): keep nothing
+        return _ops.require_extension().attn_score_fwd(
+            q.detach(), k.detach(), bias.detach(), vn.detach(), mask)
+    s = torch.tanh(q.unsqueeze(2) + k.unsqueeze(1) + bias)
+    scores = torch.einsum("bqkh,h->bqk", s, vn)
+    if mask is not None:
+        scores = scores.masked_fill(~mask.unsqueeze(1), MASKED_SCORE)
+    return scores
+
+
 # ------------------------------------------------------- depthwise conv3x3
 class _FusedDWConv3x3(torch.autograd.Function):
     @staticmethod

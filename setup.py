@@ -23,6 +23,7 @@ CSRC = ROOT / "ddlbench_amd" / "ops" / "csrc"
 # Hand-written kernel sources, pinned explicitly (torch's hipify step
 # generates *_hip.hip siblings at build time; those are never tracked).
 KERNEL_SOURCES = [
+    "attn_score.hip",
     "bindings.hip",
     "bn_act.hip",
     "conv_mfma.hip",
