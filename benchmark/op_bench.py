@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Fused-op microbenchmarks vs eager PyTorch: BN+ReLU(+add), CE,
-label-smoothed CE, attention score, SGD (--ops picks arms).
+label-smoothed CE, attention score, LSTM, SGD (--ops picks arms).
 
 Reports ms and achieved HBM GB/s per op over ResNet-50 activation
 shapes in both layouts — the evidence for the memory-bound fusion wins
@@ -160,16 +160,78 @@ def bench_attn(dev, iters, warmup, rounds=5):
         del q, k, ds, leaves
 
 
+def bench_lstm(dev, iters, warmup, rounds=5):
+    """One single-layer bf16 LSTM, the native recurrence against the library
+    path (ops.modules.LSTM backend "native" / "library"), alternated in
+    rounds in one process. Training shapes run forward + backward through
+    autograd with gradients to x and all four parameters; the decode shape
+    (T = 1, with hx) runs forward only under no_grad."""
+    from ddlbench_amd.ops.modules import LSTM
+    dt = torch.bfloat16
+    for T, B, I, H, train in ((50, 64, 1024, 1024, True),
+                              (32, 128, 2048, 1024, True),
+                              (1, 64, 2048, 1024, False)):
+        torch.manual_seed(T * B)
+        m = LSTM(I, H).to(dev).to(dt)
+        g = torch.Generator(device=dev).manual_seed(T * B + I)
+        mk = lambda *s: torch.randn(*s, device=dev, dtype=dt, generator=g)
+        x = mk(T, B, I).requires_grad_(train)
+        dy = mk(T, B, H)
+        hx = None if train else (mk(1, B, H), mk(1, B, H))
+
+        def step(backend):
+            m.backend = backend
+            if not train:
+                with torch.no_grad():
+                    m(x, hx)
+                return
+            x.grad = None
+            m.zero_grad(set_to_none=True)
+            m(x)[0].backward(dy)
+
+        times = {"native": [], "library": []}
+        peak = {}
+        for backend in times:
+            step(backend)
+            x.grad = None
+            m.zero_grad(set_to_none=True)
+            torch.cuda.synchronize()
+            base = torch.cuda.memory_allocated()
+            torch.cuda.reset_peak_memory_stats()
+            step(backend)
+            torch.cuda.synchronize()
+            # beyond x and the weights: outputs, saved state and gradients
+            peak[backend] = torch.cuda.max_memory_allocated() - base
+        for _ in range(rounds):
+            for backend in times:
+                times[backend].append(
+                    timeit(lambda: step(backend), iters, warmup))
+        med = {b: sorted(v)[len(v) // 2] for b, v in times.items()}
+        print(json.dumps({
+            "op": "lstm_fwd_bwd" if train else "lstm_fwd_decode",
+            "shape": f"T{T} B{B} I{I} H{H}", "dtype": "bfloat16",
+            "native_ms": round(med["native"] * 1e3, 4),
+            "native_ms_min": round(min(times["native"]) * 1e3, 4),
+            "library_ms": round(med["library"] * 1e3, 4),
+            "library_ms_min": round(min(times["library"]) * 1e3, 4),
+            "speedup": round(med["library"] / med["native"], 2),
+            "native_peak_MB": round(peak["native"] / 2**20, 2),
+            "library_peak_MB": round(peak["library"] / 2**20, 2)}),
+            flush=True)
+        del m, x, dy, hx
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--iters", type=int, default=20)
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--dtype", default="bfloat16")
-    p.add_argument("--ops", default="bn,ce,ls_ce,attn,sgd",
-                   help="comma-separated arms: bn, ce, ls_ce, attn, sgd")
+    p.add_argument("--ops", default="bn,ce,ls_ce,attn,lstm,sgd",
+                   help="comma-separated arms: bn, ce, ls_ce, attn, lstm, "
+                        "sgd")
     args = p.parse_args()
     arms = set(args.ops.split(","))
-    assert arms <= {"bn", "ce", "ls_ce", "attn", "sgd"}, args.ops
+    assert arms <= {"bn", "ce", "ls_ce", "attn", "lstm", "sgd"}, args.ops
     assert torch.cuda.is_available()
     from ddlbench_amd.ops import functional as NF
     dev = torch.device("cuda", 0)
@@ -267,6 +329,9 @@ def main():
 
     if "attn" in arms:
         bench_attn(dev, args.iters, args.warmup)
+
+    if "lstm" in arms:
+        bench_lstm(dev, args.iters, args.warmup)
 
     if "sgd" not in arms:
         return

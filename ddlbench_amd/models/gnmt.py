@@ -5,8 +5,8 @@ Parity with the reference's second workload
 SURVEY.md §2.12): ResidualRecurrentEncoder (emulated-bidirectional LSTM
 layer 0 + unidirectional residual LSTMs), ResidualRecurrentDecoder with
 Bahdanau RecurrentAttention and a Classifier head, hidden=1024,
-vocab=32320. LSTM cells go through torch.nn.LSTM (MIOpen RNN on ROCm);
-the emulated bidirectional layer uses the hand-written revert_varlen
+vocab=32320. LSTM layers are ops.modules.LSTM: torch.nn.LSTM (MIOpen RNN on
+ROCm) by default, the native step kernels with DDLB_LSTM=native; the emulated bidirectional layer uses the hand-written revert_varlen
 HIP kernel (ops/csrc/seq_utils.hip) with a torch fallback on CPU."""
 
 from __future__ import annotations
@@ -21,6 +21,7 @@ import torch.nn.functional as F
 
 from ddlbench_amd import ops as _ops
 from ddlbench_amd.ops import functional as NF
+from ddlbench_amd.ops.modules import LSTM
 
 PAD, BOS, EOS = 0, 1, 2
 
@@ -76,8 +77,8 @@ class EmuBidirLSTM(nn.Module):
 
     def __init__(self, input_size: int, hidden_size: int):
         super().__init__()
-        self.fwd = nn.LSTM(input_size, hidden_size)
-        self.bwd = nn.LSTM(input_size, hidden_size)
+        self.fwd = LSTM(input_size, hidden_size)
+        self.bwd = LSTM(input_size, hidden_size)
 
     def forward(self, x, lengths):
         y_f, _ = self.fwd(x)
@@ -94,9 +95,9 @@ class ResidualRecurrentEncoder(nn.Module):
         self.embedder = nn.Embedding(vocab_size, hidden_size,
                                      padding_idx=PAD)
         self.bidir = EmuBidirLSTM(hidden_size, hidden_size)
-        self.layer1 = nn.LSTM(2 * hidden_size, hidden_size)
+        self.layer1 = LSTM(2 * hidden_size, hidden_size)
         self.layers = nn.ModuleList(
-            [nn.LSTM(hidden_size, hidden_size)
+            [LSTM(hidden_size, hidden_size)
              for _ in range(num_layers - 2)])
         self.dropout = nn.Dropout(dropout)
 
@@ -165,7 +166,7 @@ class RecurrentAttention(nn.Module):
     def __init__(self, input_size: int, context_size: int,
                  hidden_size: int, dropout: float = 0.2):
         super().__init__()
-        self.rnn = nn.LSTM(input_size, hidden_size)
+        self.rnn = LSTM(input_size, hidden_size)
         self.attn = BahdanauAttention(hidden_size, context_size,
                                       hidden_size)
         self.dropout = nn.Dropout(dropout)
@@ -196,9 +197,9 @@ class ResidualRecurrentDecoder(nn.Module):
                                      padding_idx=PAD)
         self.att_rnn = RecurrentAttention(hidden_size, hidden_size,
                                           hidden_size, dropout)
-        self.layer1 = nn.LSTM(2 * hidden_size, hidden_size)
+        self.layer1 = LSTM(2 * hidden_size, hidden_size)
         self.layers = nn.ModuleList(
-            [nn.LSTM(2 * hidden_size, hidden_size)
+            [LSTM(2 * hidden_size, hidden_size)
              for _ in range(num_layers - 2)])
         self.classifier = Classifier(hidden_size, vocab_size)
         self.dropout = nn.Dropout(dropout)

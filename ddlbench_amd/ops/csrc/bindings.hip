@@ -530,6 +530,122 @@ std::vector<torch::Tensor> attn_score_bwd(torch::Tensor ds, torch::Tensor q,
   return {dq, dk, dbias, dvn};
 }
 
+// ---- LSTM recurrence ----------------------------------------------------
+// Shape, dtype, device and alignment of one tensor the step kernels read or
+// write; bf16 rows are fetched as 16-byte fragments.
+void check_lstm(const torch::Tensor& t, const char* name,
+                at::ScalarType dtype, at::IntArrayRef shape,
+                const torch::Tensor& like) {
+  check_gpu_contig(t, name);
+  TORCH_CHECK(t.scalar_type() == dtype, "lstm: ", name, " must be ",
+              dtype == at::kFloat ? "fp32" : "bf16");
+  TORCH_CHECK(t.device() == like.device(), "lstm: ", name,
+              " must be on the first tensor's device");
+  TORCH_CHECK(t.sizes() == shape, "lstm: ", name, " has shape ", t.sizes(),
+              ", expected ", shape);
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0,
+              "lstm: ", name, " must be 16-byte aligned");
+}
+
+void check_lstm_dims(int64_t T, int64_t B, int64_t H) {
+  TORCH_CHECK(T >= 1 && B >= 1, "lstm: T and B must be at least 1");
+  TORCH_CHECK(H >= 8 && H % 8 == 0, "lstm: H must be a multiple of 8");
+  TORCH_CHECK(((H + 15) / 16) * ((B + 15) / 16) < (1LL << 31),
+              "lstm: ceil(H/16) * ceil(B/16) must be below 2^31");
+}
+
+// xproj (T, B, 4H) bf16, w_hh (4H, H) bf16, bias (4H) fp32, h0 (B, H) bf16,
+// c0 (B, H) fp32 -> {y (T, B, H) bf16, cs (T, B, H) fp32, gates (T, B, 4H)
+// bf16}; gates comes back undefined unless save_gates.
+std::vector<torch::Tensor> lstm_fwd(torch::Tensor xproj, torch::Tensor w_hh,
+                                    torch::Tensor bias,
+                                    c10::optional<torch::Tensor> h0,
+                                    c10::optional<torch::Tensor> c0,
+                                    bool save_gates) {
+  TORCH_CHECK(xproj.dim() == 3 && w_hh.dim() == 2,
+              "lstm: xproj must be (T, B, 4H) and w_hh (4H, H)");
+  const int64_t T = xproj.size(0), B = xproj.size(1), H = w_hh.size(1);
+  check_lstm_dims(T, B, H);
+  check_lstm(xproj, "xproj", at::kBFloat16, {T, B, 4 * H}, xproj);
+  check_lstm(w_hh, "w_hh", at::kBFloat16, {4 * H, H}, xproj);
+  check_lstm(bias, "bias", at::kFloat, {4 * H}, xproj);
+  if (h0.has_value()) check_lstm(*h0, "h0", at::kBFloat16, {B, H}, xproj);
+  if (c0.has_value()) check_lstm(*c0, "c0", at::kFloat, {B, H}, xproj);
+
+  torch::Tensor y = torch::empty({T, B, H}, xproj.options());
+  torch::Tensor cs =
+      torch::empty({T, B, H}, xproj.options().dtype(at::kFloat));
+  torch::Tensor gates;
+  if (save_gates) gates = torch::empty({T, B, 4 * H}, xproj.options());
+
+  using bf16 = __hip_bfloat16;
+  const bf16* xp = dptr<bf16>(xproj);
+  bf16* yp = dptr<bf16>(y);
+  bf16* gp = save_gates ? dptr<bf16>(gates) : nullptr;
+  float* cp = dptr<float>(cs);
+  const bf16* h_prev = h0.has_value() ? dptr<bf16>(*h0) : nullptr;
+  const float* c_prev = c0.has_value() ? dptr<float>(*c0) : nullptr;
+  auto s = cur_stream();
+  for (int64_t t = 0; t < T; ++t) {
+    bf16* y_t = yp + t * B * H;
+    float* c_t = cp + t * B * H;
+    launch_lstm_step_fwd(h_prev, dptr<bf16>(w_hh), xp + t * B * 4 * H,
+                         dptr<float>(bias), c_prev, y_t, c_t,
+                         gp ? gp + t * B * 4 * H : nullptr, B, H, s);
+    h_prev = y_t;
+    c_prev = c_t;
+  }
+  return {y, cs, gates};
+}
+
+// dy (T, B, H) bf16, dh_T (B, H) bf16, dc_T (B, H) fp32, w_hh (4H, H) bf16,
+// gates / cs as lstm_fwd returned them, c0 as given to it
+// -> {dgates (T, B, 4H) bf16, dc0 (B, H) fp32}. W_hh is transposed once
+// here, outside the loop, so the backward product reads K-contiguous rows.
+std::vector<torch::Tensor> lstm_bwd(torch::Tensor dy,
+                                    c10::optional<torch::Tensor> dh_T,
+                                    c10::optional<torch::Tensor> dc_T,
+                                    torch::Tensor w_hh, torch::Tensor gates,
+                                    torch::Tensor cs,
+                                    c10::optional<torch::Tensor> c0) {
+  TORCH_CHECK(dy.dim() == 3, "lstm: dy must be (T, B, H)");
+  const int64_t T = dy.size(0), B = dy.size(1), H = dy.size(2);
+  check_lstm_dims(T, B, H);
+  check_lstm(dy, "dy", at::kBFloat16, {T, B, H}, dy);
+  check_lstm(w_hh, "w_hh", at::kBFloat16, {4 * H, H}, dy);
+  torch::Tensor w_hh_t = w_hh.t().contiguous();
+  check_lstm(gates, "gates", at::kBFloat16, {T, B, 4 * H}, dy);
+  check_lstm(cs, "cs", at::kFloat, {T, B, H}, dy);
+  if (dh_T.has_value()) check_lstm(*dh_T, "dh_T", at::kBFloat16, {B, H}, dy);
+  if (dc_T.has_value()) check_lstm(*dc_T, "dc_T", at::kFloat, {B, H}, dy);
+  if (c0.has_value()) check_lstm(*c0, "c0", at::kFloat, {B, H}, dy);
+
+  torch::Tensor dgates = torch::empty({T, B, 4 * H}, dy.options());
+  // dc ping-pong: step t writes half t & 1, so dc0 ends in half 0
+  torch::Tensor dc = torch::empty({2, B, H}, cs.options());
+
+  using bf16 = __hip_bfloat16;
+  bf16* dgp = dptr<bf16>(dgates);
+  float* dcp = dptr<float>(dc);
+  const float* csp = dptr<float>(cs);
+  auto s = cur_stream();
+  for (int64_t t = T - 1; t >= 0; --t) {
+    const bool last = t == T - 1;
+    const float* c_prev = t > 0 ? csp + (t - 1) * B * H
+                          : c0.has_value() ? dptr<float>(*c0) : nullptr;
+    const float* dc_in =
+        !last ? dcp + ((t + 1) & 1) * B * H
+        : dc_T.has_value() ? dptr<float>(*dc_T) : nullptr;
+    launch_lstm_step_bwd(
+        last ? nullptr : dgp + (t + 1) * B * 4 * H, dptr<bf16>(w_hh_t),
+        dptr<bf16>(dy) + t * B * H,
+        last && dh_T.has_value() ? dptr<bf16>(*dh_T) : nullptr,
+        dptr<bf16>(gates) + t * B * 4 * H, csp + t * B * H, c_prev, dc_in,
+        dgp + t * B * 4 * H, dcp + (t & 1) * B * H, B, H, s);
+  }
+  return {dgates, dc.select(0, 0)};
+}
+
 // ---- MFMA implicit-GEMM conv (NHWC bf16) ------------------------------
 // x: (N,C,H,W) logical, channels_last memory; w: (K,C,R,S) logical,
 // channels_last memory (= (K,R,S,C) image). Returns channels_last y.
@@ -974,6 +1090,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("ds"), py::arg("q"), py::arg("k"), py::arg("bias"),
         py::arg("vn"), py::arg("mask") = py::none(),
         py::arg("need_q") = true, py::arg("need_k") = true);
+  m.def("lstm_fwd", &lstm_fwd,
+        "LSTM recurrence forward: one native kernel per time step");
+  m.def("lstm_bwd", &lstm_bwd,
+        "LSTM recurrence backward: one native kernel per time step");
   m.def("revert_varlen", &revert_varlen,
         "reverse each batch element's valid time prefix (T,B,F)");
   m.def("varlen_mask", &varlen_mask, "valid-timestep mask (T,B) uint8");

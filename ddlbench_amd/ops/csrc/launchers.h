@@ -216,6 +216,22 @@ void launch_revert_varlen(const T*, T*, const int64_t*, int64_t, int64_t,
 void launch_varlen_mask(const int64_t*, uint8_t*, int64_t, int64_t,
                         hipStream_t);
 
+// ---- lstm.hip ---------------------------------------------------------
+// One time step each; bf16 tensors travel as void*. H % 8 == 0, every bf16
+// base 16-byte aligned, ceil(H/16) * ceil(B/16) below 2^31. Null h_prev /
+// c_prev / dg_next / dh_add / dc_in mean zeros; null gates is not written.
+void launch_lstm_step_fwd(const void* h_prev, const void* w,
+                          const void* xproj, const float* bias,
+                          const float* c_prev, void* y, float* cs,
+                          void* gates, int64_t B, int64_t H,
+                          hipStream_t stream);
+void launch_lstm_step_bwd(const void* dg_next, const void* wt,
+                          const void* dy, const void* dh_add,
+                          const void* gates, const float* cs,
+                          const float* c_prev, const float* dc_in, void* dg,
+                          float* dc_out, int64_t B, int64_t H,
+                          hipStream_t stream);
+
 // ---- depthwise_conv.hip -----------------------------------------------
 template <typename T>
 void launch_dw3x3_fwd(const T*, const float*, T*, int64_t, int64_t, int64_t,

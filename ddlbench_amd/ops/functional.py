@@ -237,6 +237,148 @@ def attention_score(q: torch.Tensor, k: torch.Tensor, bias: torch.Tensor,
     return scores
 
 
+# ------------------------------------------------------------------ LSTM
+def _aligned16(t: torch.Tensor) -> torch.Tensor:
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+class _NativeLSTM(torch.autograd.Function):
+    """Single-layer time-major bf16 LSTM. The two input-side GEMMs and the
+    weight-gradient GEMMs are library calls outside the time loop; the
+    recurrence is one native kernel per step, forward and backward. Saved
+    for backward: x, y, the fp32 cell states and the four activated gates
+    in bf16 (T*B*4H)."""
+
+    @staticmethod
+    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, h0, c0):
+        ext = _ops.require_extension()
+        T, B, I = x.shape
+        H = w_hh.size(1)
+        x = x.contiguous()
+        w_hh = _aligned16(w_hh)
+        xproj = torch.mm(x.view(T * B, I), w_ih.t()).view(T, B, 4 * H)
+        bias = b_ih.float() + b_hh.float()
+        h0 = _aligned16(h0) if h0 is not None else None
+        c0f = c0.float().contiguous() if c0 is not None else None
+        y, cs, gates = ext.lstm_fwd(_aligned16(xproj), w_hh, bias, h0, c0f,
+                                    True)
+        ctx.save_for_backward(x, w_ih, w_hh, y, cs, gates, h0, c0f)
+        ctx.set_materialize_grads(False)
+        ctx.bias_dtypes = (b_ih.dtype, b_hh.dtype)
+        ctx.c0_dtype = c0.dtype if c0 is not None else None
+        return y, y[-1:].clone(), cs[-1:].to(x.dtype)
+
+    @staticmethod
+    def backward(ctx, dy, dh_T, dc_T):
+        ext = _ops.require_extension()
+        x, w_ih, w_hh, y, cs, gates, h0, c0f = ctx.saved_tensors
+        T, B, I = x.shape
+        H = w_hh.size(1)
+        need = ctx.needs_input_grad
+        dy = _aligned16(dy) if dy is not None else torch.zeros_like(y)
+        if dh_T is not None:
+            dh_T = _aligned16(dh_T.reshape(B, H))
+        if dc_T is not None:
+            dc_T = dc_T.reshape(B, H).float().contiguous()
+        dgates, dc0 = ext.lstm_bwd(dy, dh_T, dc_T, w_hh, gates, cs, c0f)
+        dg2 = dgates.view(T * B, 4 * H)
+        dx = torch.mm(dg2, w_ih).view(T, B, I) if need[0] else None
+        dw_ih = torch.mm(dg2.t(), x.view(T * B, I)) if need[1] else None
+        dw_hh = None
+        if need[2]:
+            dw_hh = torch.mm(dg2[B:].t(), y[:-1].view((T - 1) * B, H))
+            if h0 is not None:
+                dw_hh = dw_hh.addmm_(dgates[0].t(), h0)
+        db = dgates.float().sum((0, 1)) if need[3] or need[4] else None
+        db_ih = db.to(ctx.bias_dtypes[0]) if need[3] else None
+        db_hh = db.to(ctx.bias_dtypes[1]) if need[4] else None
+        dh0 = torch.mm(dgates[0], w_hh) if need[5] else None
+        dc0 = dc0.to(ctx.c0_dtype) if need[6] else None
+        return dx, dw_ih, dw_hh, db_ih, db_hh, dh0, dc0
+
+
+def _lstm_native_reject(x, w_hh) -> Optional[str]:
+    """Why the native recurrence cannot run these tensors, or None."""
+    if x.device.type != "cuda":
+        return f"a {x.device.type} tensor (the kernels are HIP only)"
+    if x.dtype != torch.bfloat16 or w_hh.dtype != torch.bfloat16:
+        return (f"{x.dtype} input with {w_hh.dtype} weights (bf16 only; "
+                "there is no fp32 MFMA path)")
+    if w_hh.size(1) % 8 != 0:
+        return f"hidden size {w_hh.size(1)} (must be a multiple of 8)"
+    return None
+
+
+def _lstm_torch(x, w_ih, w_hh, b_ih, b_hh, h, c):
+    xproj = x @ w_ih.t() + (b_ih + b_hh)
+    w_hh_t = w_hh.t()
+    ys = []
+    for t in range(x.size(0)):
+        i, f, g, o = (xproj[t] + h @ w_hh_t).chunk(4, dim=1)
+        c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(g)
+        h = torch.sigmoid(o) * torch.tanh(c)
+        ys.append(h)
+    return torch.stack(ys), (h.unsqueeze(0), c.unsqueeze(0))
+
+
+def lstm(x: torch.Tensor, w_ih: torch.Tensor, w_hh: torch.Tensor,
+         b_ih: torch.Tensor, b_hh: torch.Tensor, hx=None,
+         backend: str = "auto"):
+    """Single-layer unidirectional LSTM over time-major x (T, B, I) with
+    PyTorch's parameter layout (gate rows i, f, g, o). ``hx`` is None or
+    ``(h0, c0)``, each (1, B, H). Returns ``(y, (h_T, c_T))`` with y
+    (T, B, H) and h_T, c_T (1, B, H) in x's dtype, like ``nn.LSTM``.
+
+    The native path (bf16 on a GPU, H a multiple of 8) runs the recurrence
+    in the HIP step kernels and raises NotImplementedError for anything it
+    cannot run; ``backend="torch"`` is the plain time-loop composition in
+    whatever dtype it is given."""
+    if backend not in ("auto", "native", "torch"):
+        raise ValueError("lstm backend must be auto, native or torch, got "
+                         f"{backend!r}")
+    if x.dim() != 3:
+        raise ValueError(f"lstm: x must be (T, B, I), got {tuple(x.shape)}")
+    T, B, _ = x.shape
+    H = w_hh.size(1)
+    if T < 1 or B < 1:
+        raise ValueError("lstm: T and B must be at least 1")
+    h0 = c0 = None
+    if hx is not None:
+        h0, c0 = hx
+        h0, c0 = h0.reshape(B, H), c0.reshape(B, H)
+    native = backend == "native" or (backend == "auto"
+                                     and x.device.type == "cuda")
+    if native:
+        why = _lstm_native_reject(x, w_hh)
+        if why is not None:
+            raise NotImplementedError(
+                f"native LSTM does not support {why}; pass "
+                "backend=\"torch\" for the composition")
+        _ops.require_extension()
+        tensors = (x, w_ih, w_hh, b_ih, b_hh, h0, c0)
+        if torch.is_grad_enabled() and any(
+                t is not None and t.requires_grad for t in tensors):
+            y, h_T, c_T = _NativeLSTM.apply(*tensors)
+            return y, (h_T, c_T)
+        # nothing to differentiate (greedy / beam decode): the gates are
+        # not even written
+        ext = _ops.require_extension()
+        x = x.detach().contiguous()
+        xproj = torch.mm(x.view(T * B, -1), w_ih.detach().t())
+        y, cs, _ = ext.lstm_fwd(
+            _aligned16(xproj.view(T, B, 4 * H)), _aligned16(w_hh.detach()),
+            b_ih.detach().float() + b_hh.detach().float(),
+            _aligned16(h0.detach()) if h0 is not None else None,
+            c0.detach().float().contiguous() if c0 is not None else None,
+            False)
+        return y, (y[-1:].clone(), cs[-1:].to(x.dtype))
+    if h0 is None:
+        h0 = x.new_zeros(B, H)
+        c0 = x.new_zeros(B, H)
+    return _lstm_torch(x, w_ih, w_hh, b_ih, b_hh, h0, c0)
+
+
 # ------------------------------------------------------- depthwise conv3x3
 class _FusedDWConv3x3(torch.autograd.Function):
     @staticmethod

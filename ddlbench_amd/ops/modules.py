@@ -3,10 +3,12 @@
 ``BNAct`` replaces the BatchNorm2d → ReLU (→ residual add) chains of the
 model zoo with one fused op; ``DepthwiseConv3x3`` replaces
 Conv2d(groups=channels). Both keep plain-PyTorch semantics (state dict
-compatible with nn.BatchNorm2d / nn.Conv2d field names)."""
+compatible with nn.BatchNorm2d / nn.Conv2d field names). ``LSTM`` is
+nn.LSTM with a choice of recurrence backend."""
 
 from __future__ import annotations
 
+import os
 from typing import Optional
 
 import torch
@@ -104,6 +106,61 @@ class DepthwiseConv3x3(nn.Module):
 
     def extra_repr(self) -> str:
         return f"{self.channels}, stride={self.stride}"
+
+
+class LSTM(nn.LSTM):
+    """``torch.nn.LSTM`` with a choice of recurrence: same parameters, same
+    registration order (so the same seeded initial values) and the same
+    ``state_dict`` keys. ``backend`` is "auto", "native" or "library";
+    while it is "auto", DDLB_LSTM picks one per call, and "auto" itself is
+    the library path. "native" runs ``NF.lstm``'s HIP step kernels and
+    raises NotImplementedError for anything they cannot run."""
+
+    def __init__(self, *args, backend: str = "auto", **kwargs):
+        super().__init__(*args, **kwargs)
+        self.backend = backend
+
+    def resolve_backend(self) -> str:
+        """The backend the next forward uses; the environment is read here,
+        per call, and only while the module's own setting is "auto"."""
+        backend = self.backend
+        if backend == "auto":
+            backend = os.environ.get("DDLB_LSTM", "auto")
+        if backend not in ("auto", "native", "library"):
+            raise ValueError("LSTM backend must be auto, native or library, "
+                             f"got {backend!r}")
+        return "library" if backend == "auto" else backend
+
+    def _native_reject(self, x) -> Optional[str]:
+        if isinstance(x, nn.utils.rnn.PackedSequence):
+            return "a PackedSequence input"
+        if self.num_layers != 1:
+            return f"num_layers={self.num_layers}"
+        if self.bidirectional:
+            return "bidirectional=True"
+        if self.proj_size != 0:
+            return f"proj_size={self.proj_size}"
+        if self.dropout != 0:
+            return f"inner dropout={self.dropout}"
+        if self.batch_first:
+            return "batch_first=True"
+        if not self.bias:
+            return "bias=False"
+        if x.dim() != 3:
+            return "unbatched input"
+        return None
+
+    def forward(self, input, hx=None):
+        if self.resolve_backend() == "library":
+            return super().forward(input, hx)
+        why = self._native_reject(input)
+        if why is not None:
+            raise NotImplementedError(
+                f"native LSTM does not support {why}; use "
+                "backend=\"library\"")
+        return NF.lstm(input, self.weight_ih_l0, self.weight_hh_l0,
+                       self.bias_ih_l0, self.bias_hh_l0, hx,
+                       backend="native")
 
 
 class CrossEntropyLoss(nn.Module):

@@ -34,6 +34,7 @@ KERNEL_SOURCES = [
     "cross_entropy.hip",
     "depthwise_conv.hip",
     "fused_sgd.hip",
+    "lstm.hip",
     "maxpool.hip",
     "seq_utils.hip",
 ]
