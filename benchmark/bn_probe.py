@@ -74,13 +74,19 @@ def main():
                                                g, 1, True, True, True,
                                                mask))
                    if mask is not None else float("nan"))
+            # the same backward without the dres write (gated shortcut)
+            tbn = (t_ms(lambda: ext.bn_act_bwd(dy, None, x, mean, invstd,
+                                               g, 1, True, False, True,
+                                               mask))
+                   if mask is not None else float("nan"))
             row.update(rep=rep, fwd_ms=round(tf, 3),
                        fwd_TBs=round(4 * nb / tf, 2),
                        apply_ms=round(te, 3),
                        apply_TBs=round(3 * nb / te, 2),
                        stats_TBs=round(nb / max(tf - te, 1e-5), 2),
                        bwd_ms=round(tb, 3), bwd_TBs=round(8 * nb / tb, 2),
-                       bwdmask_ms=round(tbm, 3))
+                       bwdmask_ms=round(tbm, 3),
+                       bwdmask_nodres_ms=round(tbn, 3))
             print(json.dumps(row), flush=True)
 
 

@@ -8,8 +8,10 @@ dispatch policy.
 
 Each row also carries the residual-join columns: ``mfma2_dgrad_add_ms``
 is the data-grad with the shortcut's gradient summed in its epilogue
-(``conv_igemm_dgrad(..., add=g)``), ``mfma2_dgrad_then_add_ms`` the plain
-data-grad followed by the torch bf16 add it replaces. ``--join`` prints
+(``conv_igemm_dgrad(..., add=g)``), ``mfma2_dgrad_add_gated_ms`` the same
+with the addend gated by a 1-bit mask (``gate=m``),
+``mfma2_dgrad_then_add_ms`` the plain data-grad followed by the torch bf16
+add it replaces. ``--join`` prints
 only those (plus the plain data-grad) per shape.
 
 ``--stem`` instead times the small-C stem convs the model zoo builds
@@ -131,10 +133,15 @@ def join_columns(ext, dy, w_perm, x, stride, pad, args):
     (deep-pipeline structure; g stands in for the shortcut's gradient)."""
     N, C, H, W = x.shape
     g = torch.randn_like(x)
+    m = torch.randint(0, 256, (x.numel() // 8,), device=x.device,
+                      dtype=torch.uint8)
     os.environ["DDLB_CONV_V2"] = "1"
     fns = {
         "mfma2_dgrad_add_ms": lambda: ext.conv_igemm_dgrad(
             dy, w_perm, N, C, H, W, stride, pad, add=g),
+        # the addend gated by a 1-bit mask in the same epilogue
+        "mfma2_dgrad_add_gated_ms": lambda: ext.conv_igemm_dgrad(
+            dy, w_perm, N, C, H, W, stride, pad, add=g, gate=m),
         "mfma2_dgrad_then_add_ms": lambda: ext.conv_igemm_dgrad(
             dy, w_perm, N, C, H, W, stride, pad) + g,
     }

@@ -17,6 +17,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ddlbench_amd.ops.functional import GateSlot, gate_enabled
 from ddlbench_amd.ops.modules import BNAct
 
 
@@ -35,8 +36,8 @@ class Downsample(nn.Module):
         self.conv = conv1x1(cin, cout, stride)
         self.bn = BNAct(cout, act="none")
 
-    def forward(self, x):
-        return self.bn(self.conv(x))
+    def forward(self, x, gate=None):
+        return self.bn(self.conv(x), gate=gate)
 
 
 def _joins(conv1, x):
@@ -47,6 +48,22 @@ def _joins(conv1, x):
     are summed inside the data-grad kernel."""
     return (hasattr(conv1, "forward_join") and x.is_cuda
             and x.dtype == torch.bfloat16)
+
+
+def _fork(block, x):
+    """``(conv1(x), identity, slot)`` of a joining block. ``slot`` is the
+    forward's GateSlot (None with DDLB_GATE=0): the join BN gets it as the
+    producer of the shortcut gradient, and exactly one consumer got it
+    here — conv1 when the shortcut is the input itself, else the
+    downsample BN — so that gradient is handed over as the join's output
+    gradient plus the ReLU mask and never written."""
+    slot = GateSlot() if gate_enabled() else None
+    if block.downsample is None:
+        out, identity = block.conv1.forward_join(x, gate=slot)
+    else:
+        out, skip = block.conv1.forward_join(x)
+        identity = block.downsample(skip, gate=slot)
+    return out, identity, slot
 
 
 class BasicBlock(nn.Module):
@@ -63,15 +80,14 @@ class BasicBlock(nn.Module):
             self.downsample = Downsample(cin, planes * self.expansion, stride)
 
     def forward(self, x):
+        slot = None
         if _joins(self.conv1, x):
-            out, skip = self.conv1.forward_join(x)
-            identity = (skip if self.downsample is None
-                        else self.downsample(skip))
+            out, identity, slot = _fork(self, x)
             out = self.bn1(out)
         else:
             identity = x if self.downsample is None else self.downsample(x)
             out = self.bn1(self.conv1(x))
-        return self.bn2(self.conv2(out), res=identity)
+        return self.bn2(self.conv2(out), res=identity, gate=slot)
 
 
 class Bottleneck(nn.Module):
@@ -97,16 +113,15 @@ class Bottleneck(nn.Module):
             self.downsample = Downsample(cin, planes * self.expansion, stride)
 
     def forward(self, x):
+        slot = None
         if _joins(self.conv1, x):
-            out, skip = self.conv1.forward_join(x)
-            identity = (skip if self.downsample is None
-                        else self.downsample(skip))
+            out, identity, slot = _fork(self, x)
             out = self.bn1(out)
         else:
             identity = x if self.downsample is None else self.downsample(x)
             out = self.bn1(self.conv1(x))
         out = self.bn2(self.conv2(out))
-        return self.bn3(self.conv3(out), res=identity)
+        return self.bn3(self.conv3(out), res=identity, gate=slot)
 
 
 class BottleneckX(Bottleneck):

@@ -43,8 +43,9 @@ def _dw_to_weight_layout(dw32, weight):
     return dw32.view(K, R, S, C).permute(0, 3, 1, 2).to(weight.dtype)
 
 
-def _conv_backward(ctx, dy, add=None):
-    """dx (+ add, fused into the dgrad epilogue) and dw of a native conv."""
+def _conv_backward(ctx, dy, add=None, gate=None):
+    """dx (+ add, fused into the dgrad epilogue) and dw of a native conv.
+    ``gate`` is the 1-bit mask still to be applied to ``add``."""
     ext = _ops.require_extension()
     x, weight = ctx.saved_tensors
     dy = dy.contiguous(memory_format=_CL)
@@ -58,7 +59,7 @@ def _conv_backward(ctx, dy, add=None):
             w_perm = weight.permute(1, 2, 3, 0).contiguous()
         dx = ext.conv_igemm_dgrad(dy, w_perm, x.size(0), x.size(1),
                                   x.size(2), x.size(3), ctx.stride,
-                                  ctx.pad, add)
+                                  ctx.pad, add, gate)
     if ctx.needs_input_grad[1]:
         if _WGRAD == "mfma" and NATIVE_TAIL \
                 and weight.dtype == torch.bfloat16:
@@ -107,29 +108,44 @@ class _ConvMFMAJoin(torch.autograd.Function):
     the backward hands the shortcut's to the dgrad kernel as its epilogue
     addend instead of leaving a separate bf16 add to autograd. The caller
     guarantees ``x`` is channels_last (``Conv2dMFMA.forward_join``), so
-    nothing beyond what ``_ConvMFMA`` saves is kept alive."""
+    nothing beyond what ``_ConvMFMA`` saves is kept alive.
+
+    ``slot`` (a ``functional.GateSlot`` or None) makes this node the
+    consumer of the join's gated shortcut gradient: an armed slot means
+    ``dskip`` is the join's own output gradient, and the dgrad epilogue
+    applies the slot's mask to it."""
 
     @staticmethod
-    def forward(ctx, x, weight, stride, pad):
+    def forward(ctx, x, weight, stride, pad, slot=None):
         ext = _ops.require_extension()
         w = weight.contiguous(memory_format=_CL)
         y = ext.conv_igemm_fwd(x, w, stride, pad)
         ctx.save_for_backward(x, weight)
         ctx.stride = stride
         ctx.pad = pad
+        ctx.slot = slot
+        if slot is not None:
+            slot.claim()
         # an unused shortcut arrives as dskip=None, not as a zero tensor
         ctx.set_materialize_grads(False)
         return y, x
 
     @staticmethod
     def backward(ctx, dy, dskip):
+        gate = None
+        if ctx.slot is not None and ctx.slot.armed:
+            gate = ctx.slot.take(dskip)
         if dy is None:
+            if gate is not None:
+                raise RuntimeError(
+                    "gated shortcut gradient: the conv output of a "
+                    "forward_join with a gate slot must be used")
             # only the shortcut was used: its gradient passes through
-            return dskip, None, None, None
+            return dskip, None, None, None, None
         if dskip is not None:
             dskip = dskip.contiguous(memory_format=_CL)
-        dx, dw = _conv_backward(ctx, dy, dskip)
-        return dx, dw, None, None
+        dx, dw = _conv_backward(ctx, dy, dskip, gate)
+        return dx, dw, None, None, None
 
 
 def join_enabled() -> bool:
@@ -187,16 +203,21 @@ class Conv2dMFMA(_NativeConv2d):
     def native(self, x):
         return conv2d_mfma(x, self.weight, self.stride, self.padding)
 
-    def forward_join(self, x):
+    def forward_join(self, x, gate=None):
         """``(conv(x), skip)`` for a block whose input also feeds its
         shortcut: take the shortcut from ``skip`` and the two gradients
         meeting at ``x`` are summed in the dgrad epilogue. Inputs the
         fused path does not cover (not a channels_last bf16 device
-        tensor, or DDLB_JOIN=0) get the plain conv and ``x`` itself."""
+        tensor, or DDLB_JOIN=0) get the plain conv and ``x`` itself.
+
+        ``gate`` is the block's ``functional.GateSlot`` when ``skip``
+        goes straight into the residual join: the fused path claims it
+        and its backward applies the join's mask to the shortcut
+        gradient; the plain path leaves it unclaimed."""
         if (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4
                 and x.is_contiguous(memory_format=_CL) and join_enabled()):
             return _ConvMFMAJoin.apply(x, self.weight, self.stride,
-                                       self.padding)
+                                       self.padding, gate)
         return self.forward(x), x
 
 

@@ -241,6 +241,12 @@ std::vector<torch::Tensor> bn_act_fwd(
   return {y, mean, invstd};
 }
 
+// gate: a foreign 1-bit mask for an act == 0 layer whose dy is the shortcut
+// gradient of a residual join, handed over ungated: the join's ReLU mask
+// (numel/8 bytes, the fused apply's bit order). dy' = dy * bit is formed in
+// fp32 inside the masked reduce and dx kernels, which take the act code
+// from the gate, not from the layer, so the results equal those on a
+// materialised bf16(dy * bit) bit for bit.
 std::vector<torch::Tensor> bn_act_bwd(torch::Tensor dy,
                                       c10::optional<torch::Tensor> y_opt,
                                       torch::Tensor x, torch::Tensor mean,
@@ -248,8 +254,24 @@ std::vector<torch::Tensor> bn_act_bwd(torch::Tensor dy,
                                       torch::Tensor gamma, int64_t act,
                                       bool training, bool need_dres,
                                       bool nhwc,
-                                      c10::optional<torch::Tensor> msk) {
+                                      c10::optional<torch::Tensor> msk,
+                                      c10::optional<torch::Tensor> gate) {
   TORCH_CHECK(dy.is_cuda(), "dy must be on the HIP device");
+  if (gate) {
+    TORCH_CHECK(act == 0 && !msk && !need_dres,
+                "bn_act_bwd: a foreign gate is for an act == 0 layer with "
+                "no mask and no residual of its own");
+    TORCH_CHECK(is_bf16(x) && nhwc,
+                "bn_act_bwd: a foreign gate needs bf16 NHWC tensors");
+    TORCH_CHECK(gate->is_cuda() && gate->device() == dy.device() &&
+                    gate->scalar_type() == at::kByte &&
+                    gate->is_contiguous(),
+                "bn_act_bwd: the gate must be a contiguous uint8 tensor on "
+                "dy's device");
+    // the masked ReLU-gated kernels read nothing of the act but the bits
+    msk = gate;
+    act = 1;
+  }
   TORCH_CHECK(y_opt || msk,
               "bn_act_bwd needs y or the 1-bit activation mask");
   TORCH_CHECK(dy.sizes() == x.sizes(), "dy and x differ in size");
@@ -267,6 +289,11 @@ std::vector<torch::Tensor> bn_act_bwd(torch::Tensor dy,
   TORCH_CHECK(y_opt || (plan.reduce_gate != BnGate::y &&
                         plan.dx_gate != BnGate::y),
               "bn_act_bwd: no masked kernel for this shape, y is needed");
+  TORCH_CHECK(!gate || (plan.reduce_gate == BnGate::mask &&
+                        plan.dx_gate == BnGate::mask &&
+                        plan.dx == BnElt::fixed_channel),
+              "bn_act_bwd: no masked kernel for this shape, the foreign "
+              "gate cannot be applied");
   auto s = cur_stream();
   auto fopt = x.options().dtype(at::kFloat);
   const BnWorkspace ws = bn_workspace(x, plan);
@@ -667,7 +694,7 @@ torch::Tensor conv_igemm_fwd(torch::Tensor x, torch::Tensor w,
   launch_conv_igemm(x.data_ptr(), w.data_ptr(), y.data_ptr(),
                     zero_page(x).data_ptr(), N, H, W, C, K, OH, OW, R, S,
                     (int)stride, (int)pad, /*dgrad=*/0, /*add=*/nullptr,
-                    cur_stream());
+                    /*gate=*/nullptr, cur_stream());
   return y;
 }
 
@@ -680,10 +707,16 @@ torch::Tensor conv_igemm_fwd(torch::Tensor x, torch::Tensor w,
 // one bf16 add). The kernels' epilogues do the add wherever every dx
 // element is written exactly once; the one case that relies on a
 // pre-zeroed dx (stride 2 with R==1 or S==1) adds after the launch.
+// gate: optional, with add only: numel/8 bytes holding one bit per element
+// of add in its channels_last memory order (bit i&7 of byte i/8, the mask
+// the fused BN apply writes; C % 8 == 0). The addend is then
+// bf16(float(add) * bit): what the BN backward at a residual join stores
+// as its shortcut gradient, formed here from its dy and mask instead.
 torch::Tensor conv_igemm_dgrad(torch::Tensor dy, torch::Tensor w_perm,
                                int64_t N, int64_t C, int64_t H, int64_t W,
                                int64_t stride, int64_t pad,
-                               c10::optional<torch::Tensor> add) {
+                               c10::optional<torch::Tensor> add,
+                               c10::optional<torch::Tensor> gate) {
   TORCH_CHECK(dy.dim() == 4 && w_perm.dim() == 4,
               "conv_igemm: 4-D tensors only");
   check_conv_operand(dy, "dy", "conv_igemm");
@@ -699,6 +732,17 @@ torch::Tensor conv_igemm_dgrad(torch::Tensor dy, torch::Tensor w_perm,
                 "add must have dx's shape (N,C,H,W)");
     TORCH_CHECK(add->device() == dy.device(),
                 "add must be on dy's device");
+  }
+  if (gate) {
+    TORCH_CHECK(add.has_value(), "conv_igemm: gate is legal only with add");
+    TORCH_CHECK(C % 8 == 0, "conv_igemm: gate needs C % 8 == 0");
+    TORCH_CHECK(gate->is_cuda() && gate->device() == dy.device() &&
+                    gate->scalar_type() == at::kByte &&
+                    gate->is_contiguous(),
+                "conv_igemm: gate must be a contiguous uint8 tensor on dy's "
+                "device");
+    TORCH_CHECK(gate->numel() == N * C * H * W / 8,
+                "conv_igemm: gate must hold dx.numel()/8 bytes");
   }
   const int K = dy.size(1), OH = dy.size(2), OW = dy.size(3);
   const int R = w_perm.size(1), S = w_perm.size(2);
@@ -718,8 +762,19 @@ torch::Tensor conv_igemm_dgrad(torch::Tensor dy, torch::Tensor w_perm,
                     zero_page(dy).data_ptr(), (int)N, (int)H, (int)W,
                     (int)C, K, OH, OW, R, S, (int)stride, (int)pad,
                     /*dgrad=*/1, add && !sparse ? add->data_ptr() : nullptr,
+                    gate && !sparse ? gate->data_ptr() : nullptr,
                     cur_stream());
-  if (add && sparse) dx.add_(*add);
+  if (add && sparse) {
+    if (gate) {
+      // no in-kernel add on this path: materialise the gated addend
+      auto gated = torch::empty_like(*add);
+      launch_gate_addend(add->data_ptr(), gate->data_ptr(),
+                         gated.data_ptr(), add->numel() / 8, cur_stream());
+      dx.add_(gated);
+    } else {
+      dx.add_(*add);
+    }
+  }
   return dx;
 }
 
@@ -1038,7 +1093,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fused_sgd", &fused_sgd, "fused multi-tensor SGD step");
   m.def("fused_adam", &fused_adam, "fused multi-tensor Adam/AdamW step");
   m.def("bn_act_fwd", &bn_act_fwd, "fused BN+act(+res) forward");
-  m.def("bn_act_bwd", &bn_act_bwd, "fused BN+act(+res) backward");
+  m.def("bn_act_bwd", &bn_act_bwd, "fused BN+act(+res) backward",
+        py::arg("dy"), py::arg("y"), py::arg("x"), py::arg("mean"),
+        py::arg("invstd"), py::arg("gamma"), py::arg("act"),
+        py::arg("training"), py::arg("need_dres"), py::arg("nhwc"),
+        py::arg("msk"), py::arg("gate") = py::none());
   m.def("bn_plan", &bn_plan_py,
         "the dispatch plan the BN+act launchers walk (no device needed)",
         py::arg("N"), py::arg("C"), py::arg("HW"), py::arg("nhwc"),
@@ -1052,7 +1111,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "NHWC bf16 MFMA implicit-GEMM conv data-grad (+ optional addend)",
         py::arg("dy"), py::arg("w_perm"), py::arg("N"), py::arg("C"),
         py::arg("H"), py::arg("W"), py::arg("stride"), py::arg("pad"),
-        py::arg("add") = py::none());
+        py::arg("add") = py::none(), py::arg("gate") = py::none());
   m.def("conv_igemm_wgrad", &conv_igemm_wgrad,
         "NHWC bf16 MFMA implicit-GEMM conv weight-grad (fp32 out)");
   m.def("conv_igemm_wgrad_bf16", &conv_igemm_wgrad_bf16,

@@ -108,7 +108,9 @@ DEV const bf16* b_chunk_addr(const ConvParams& p, long row, long kkg) {
 // (WR x WC) each owning a (BM_/WR x BN_/WC) sub-tile.
 // ADD: dgrad epilogue adds p.add (same rounding order as the deep-pipeline
 // kernel: round the accumulator to bf16, then one bf16 add).
-template <int MODE, int BM_, int BN_, int WR, int WC, bool ADD>
+// GATE (with ADD): the addend is p.add gated by the 1-bit mask p.gate.
+template <int MODE, int BM_, int BN_, int WR, int WC, bool ADD,
+          bool GATE = false>
 __global__ __launch_bounds__(THREADS, 2)
 void conv_igemm_kernel(ConvParams p) {
   constexpr int WM = BM_ / WR;        // wave tile M
@@ -117,6 +119,7 @@ void conv_igemm_kernel(ConvParams p) {
   constexpr int NF = WN / 16;         // N fragments per wave
   constexpr int CA = BM_ * BK / 8 / THREADS;  // A chunks per thread
   constexpr int CB = BN_ * BK / 8 / THREADS;  // B chunks per thread
+  static_assert(ADD || !GATE, "the gate applies to the addend");
   static_assert(WR * WC == 4, "4 waves");
   static_assert(CA >= 1 && CB >= 1, "tile vs thread count");
 
@@ -240,7 +243,12 @@ void conv_igemm_kernel(ConvParams p) {
         if (col < p.Nd) {
           const long o = out_row * p.Nd + col;
           bf16 v = from_f32<bf16>(acc[mf][nf][reg]);
-          if (ADD) v = from_f32<bf16>(to_f32(v) + to_f32(p.add[o]));
+          if (GATE)
+            v = from_f32<bf16>(
+                to_f32(v) +
+                to_f32(p.add[o]) * (float)((p.gate[o >> 3] >> (o & 7)) & 1));
+          else if (ADD)
+            v = from_f32<bf16>(to_f32(v) + to_f32(p.add[o]));
           p.out[o] = v;
         }
       }
@@ -336,19 +344,23 @@ void ddlb::launch_conv_igemm(const void* a, const void* b, void* out,
                              const void* zero, int N, int H, int W, int Cin,
                              int K, int OH, int OW, int R, int S, int stride,
                              int pad, int dgrad, const void* add,
-                             hipStream_t stream) {
+                             const void* gate, hipStream_t stream) {
   // the addend needs every dx element written exactly once: FPROP has
   // no addend, and stride-2 classes with R==1 or S==1 leave pixels to
   // the caller's zero fill (the binding adds after the launch there)
   if (add && (!dgrad || (stride == 2 && K % 8 == 0 && (R == 1 || S == 1))))
     throw std::invalid_argument(
         "launch_conv_igemm: addend unsupported for this pass");
+  if (gate && (!add || Cin % 8 != 0))
+    throw std::invalid_argument(
+        "launch_conv_igemm: the gate needs an addend and C % 8 == 0");
   ConvParams p;
   p.a = (const bf16*)a;
   p.b = (const bf16*)b;
   p.out = (bf16*)out;
   p.zero = (const bf16*)zero;
   p.add = (const bf16*)add;
+  p.gate = (const unsigned char*)gate;
   fill_dims(p, N, H, W, Cin, K, OH, OW, R, S, stride, pad, dgrad);
 
 #define LAUNCH(MODE, BM_, BN_, WR, WC)                                      \
@@ -356,7 +368,13 @@ void ddlb::launch_conv_igemm(const void* a, const void* b, void* out,
     const long nbm = (p.M + (BM_) - 1) / (BM_);                             \
     const long nbn = (p.Nd + (BN_) - 1) / (BN_);                            \
     const size_t lds_bytes = 2 * ((BM_) + (BN_)) * BK * sizeof(bf16);       \
-    if ((MODE) != 0 && p.add)                                               \
+    if ((MODE) != 0 && p.add && p.gate)                                     \
+      hipLaunchKernelGGL(                                                   \
+          (conv_igemm_kernel<MODE, BM_, BN_, WR, WC, (MODE) != 0,           \
+                             (MODE) != 0>),                                 \
+          dim3((unsigned)(nbm * nbn)), dim3(THREADS), lds_bytes, stream,    \
+          p);                                                               \
+    else if ((MODE) != 0 && p.add)                                          \
       hipLaunchKernelGGL(                                                   \
           (conv_igemm_kernel<MODE, BM_, BN_, WR, WC, (MODE) != 0>),         \
           dim3((unsigned)(nbm * nbn)), dim3(THREADS), lds_bytes, stream,    \
@@ -389,5 +407,42 @@ void ddlb::launch_conv_igemm(const void* a, const void* b, void* out,
   }
 #undef LAUNCH_TILED
 #undef LAUNCH
+  HIP_CHECK_LAST();
+}
+
+// ---- gated addend, materialised ---------------------------------------
+// out = bf16(float(add) * g) over n8 8-element chunks, g the chunk's mask
+// byte: the fallback for dgrad passes with no in-kernel add (the sparse
+// stride-2 case, where the binding adds after the launch).
+namespace {
+typedef __attribute__((ext_vector_type(8))) unsigned short gate_u16x8;
+
+__global__ void gate_addend_kernel(const bf16* __restrict__ add,
+                                   const unsigned char* __restrict__ gate,
+                                   bf16* __restrict__ out, long n8) {
+  const long stride = (long)gridDim.x * blockDim.x;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8;
+       i += stride) {
+    gate_u16x8 v = reinterpret_cast<const gate_u16x8*>(add)[i];
+    const unsigned g = gate[i];
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      // the product is v, a signed zero or a NaN: its low 16 bits are 0
+      v[j] = (unsigned short)(__float_as_uint(
+                                  __uint_as_float((unsigned)v[j] << 16) *
+                                  (float)((g >> j) & 1u)) >> 16);
+    reinterpret_cast<gate_u16x8*>(out)[i] = v;
+  }
+}
+}  // namespace
+
+void ddlb::launch_gate_addend(const void* add, const void* gate, void* out,
+                              long n8, hipStream_t stream) {
+  if (n8 <= 0) return;
+  const long want = (n8 + THREADS - 1) / THREADS;
+  const unsigned blocks = (unsigned)(want < 2048 ? want : 2048);
+  hipLaunchKernelGGL(gate_addend_kernel, dim3(blocks), dim3(THREADS), 0,
+                     stream, (const bf16*)add, (const unsigned char*)gate,
+                     (bf16*)out, n8);
   HIP_CHECK_LAST();
 }

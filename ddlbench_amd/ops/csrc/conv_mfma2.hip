@@ -171,7 +171,11 @@ DEV const bf16* b_slot_addr(const ConvParams& p, const Cursor& cu,
 // ADD: the dgrad epilogue adds p.add (the residual join's other
 // gradient) to the bf16-rounded tile before the store; ADD=false is the
 // plain kernel, instruction for instruction.
-template <int MODE, int BM_, int BN_, int WR, int WC, bool LIN, bool ADD>
+// GATE (with ADD): the addend is p.add gated by the 1-bit mask p.gate —
+// the thread that pre-loads an 8-element addend chunk also loads the one
+// mask byte that covers it (Nd % 8 == 0) and applies the bits in the add.
+template <int MODE, int BM_, int BN_, int WR, int WC, bool LIN, bool ADD,
+          bool GATE = false>
 __global__ __launch_bounds__(THREADS2, 2)
 void conv_igemm2_kernel(ConvParams p) {
   constexpr int WM = BM_ / WR;       // wave tile M
@@ -181,6 +185,7 @@ void conv_igemm2_kernel(ConvParams p) {
   constexpr int GA = BM_ * 32 / 8 / THREADS2;  // A glds per wave/slot
   constexpr bool COMB_B = (BN_ * 32 / 8) < THREADS2;
   constexpr int GB = COMB_B ? 1 : BN_ * 32 / 8 / THREADS2;
+  static_assert(ADD || !GATE, "the gate applies to the addend");
   static_assert(WR * WC == 8, "8 waves");
   static_assert(GA >= 1 && MF >= 1, "tile vs thread count");
   static_assert(!COMB_B || BN_ == 64, "combined-B staging needs BN=64");
@@ -367,6 +372,7 @@ void conv_igemm2_kernel(ConvParams p) {
     // state and fragments are dead by now; ITERS*4 VGPRs fit under the
     // main loop's peak.
     u16x8 addv[ADD ? ITERS : 1];
+    unsigned gatev[GATE ? ITERS : 1];
     if (ADD) {
 #pragma unroll
       for (int it = 0; it < ITERS; ++it) {
@@ -376,11 +382,13 @@ void conv_igemm2_kernel(ConvParams p) {
         const long row = bm + r;
         const long colbase = bn + ck * 8;
         addv[it] = u16x8{0, 0, 0, 0, 0, 0, 0, 0};
+        if (GATE) gatev[it] = 0;
         if (row < p.M && colbase + 8 <= p.Nd) {
           const long out_row =
               (MODE == 2) ? conv_class_dx_row(p, row) : row;
           addv[it] = *reinterpret_cast<const u16x8*>(
               p.add + out_row * p.Nd + colbase);
+          if (GATE) gatev[it] = p.gate[(out_row * p.Nd + colbase) >> 3];
         }
       }
     }
@@ -407,7 +415,12 @@ void conv_igemm2_kernel(ConvParams p) {
       const bf16* src = img + r * BN_ + ck * 8;
       if (colbase + 8 <= p.Nd) {
         u16x8 v = *reinterpret_cast<const u16x8*>(src);
-        if (ADD) {
+        if (GATE) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            v[j] = conv_bf16_add_gated_bits(v[j], addv[it][j],
+                                            gatev[it] >> j);
+        } else if (ADD) {
 #pragma unroll
           for (int j = 0; j < 8; ++j)
             v[j] = conv_bf16_add_bits(v[j], addv[it][j]);
@@ -416,7 +429,11 @@ void conv_igemm2_kernel(ConvParams p) {
       } else if (colbase < p.Nd) {
         for (int j = 0; j < (int)(p.Nd - colbase); ++j) {
           const long o = out_row * p.Nd + colbase + j;
-          if (ADD)
+          if (GATE)
+            p.out[o] = from_f32<bf16>(
+                to_f32(src[j]) +
+                to_f32(p.add[o]) * (float)((p.gate[o >> 3] >> (o & 7)) & 1));
+          else if (ADD)
             p.out[o] = from_f32<bf16>(to_f32(src[j]) + to_f32(p.add[o]));
           else
             p.out[o] = src[j];
@@ -431,8 +448,15 @@ void launch_tile(const ConvParams& p, hipStream_t stream) {
   const long nbm = (p.M + BM_ - 1) / BM_;
   const long nbn = (p.Nd + BN_ - 1) / BN_;
   const size_t lds_bytes = 4 * (BM_ + BN_) * 32 * sizeof(bf16);
-  // the addend variant exists for the dgrad modes only
+  // the addend variants exist for the dgrad modes only
   if constexpr (MODE != 0) {
+    if (p.add && p.gate) {
+      hipLaunchKernelGGL(
+          (conv_igemm2_kernel<MODE, BM_, BN_, WR, WC, LIN, true, true>),
+          dim3((unsigned)(nbm * nbn)), dim3(THREADS2), lds_bytes, stream,
+          p);
+      return;
+    }
     if (p.add) {
       hipLaunchKernelGGL(
           (conv_igemm2_kernel<MODE, BM_, BN_, WR, WC, LIN, true>),

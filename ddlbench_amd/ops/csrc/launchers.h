@@ -127,12 +127,18 @@ void launch_attn_score_bwd(const T* ds, const T* q, const T* k,
 // ---- conv_mfma.hip: forward (dgrad=0) or data-grad (dgrad=1); the dims
 // are always those of the forward conv. add (dgrad only, nullptr = none)
 // is a read-only bf16 tensor of dx's geometry summed into dx in the
-// epilogue; stride-2 with R==1 or S==1 does not take one (throws) ------
+// epilogue; stride-2 with R==1 or S==1 does not take one (throws). gate
+// (with add only, Cin % 8 == 0, nullptr = none) holds one bit per element
+// of add, bit i&7 of byte i/8: the epilogue then adds bf16(add * bit) ---
 void launch_conv_igemm(const void* a, const void* b, void* out,
                        const void* zero, int N, int H, int W, int Cin,
                        int K, int OH, int OW, int R, int S, int stride,
                        int pad, int dgrad, const void* add,
-                       hipStream_t stream);
+                       const void* gate, hipStream_t stream);
+// out = bf16(add * bit) over n8 8-element chunks, materialised: for the
+// dgrad passes whose add runs outside the kernel
+void launch_gate_addend(const void* add, const void* gate, void* out,
+                        long n8, hipStream_t stream);
 
 // The launches launch_conv_igemm makes for a shape, as pure host data:
 // the launcher walks this plan, and the bindings expose it so tests can

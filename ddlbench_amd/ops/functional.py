@@ -6,6 +6,7 @@ error there if the extension is missing), torch composition on CPU."""
 
 from __future__ import annotations
 
+import os
 from typing import Optional
 
 import torch
@@ -36,11 +37,78 @@ def _apply_act(v: torch.Tensor, act: str) -> torch.Tensor:
     return v
 
 
+# ------------------------------------------------- gated shortcut gradient
+def gate_enabled() -> bool:
+    """DDLB_GATE=0 (read per call) restores the materialised shortcut
+    gradient at the residual joins."""
+    return os.environ.get("DDLB_GATE", "1") != "0"
+
+
+class GateSlot:
+    """Hand-over of one residual join's shortcut gradient without writing
+    it. At ``z = relu(bn(y) + res)`` the gradient of ``res`` is ``dz`` with
+    the ReLU mask applied and nothing else, and it is read exactly once. A
+    block creates one slot per forward and gives it to the join's BN (the
+    producer) and to the one op whose backward receives that gradient (the
+    consumer: the block's first conv through ``forward_join``, or the
+    downsample BN).
+
+    forward   the consumer claims the slot when it takes the path that can
+              apply a gate; the producer, which runs after it, uses the slot
+              only if it is claimed and its own forward wrote a mask.
+    backward  the producer returns ``dz`` itself as the gradient of ``res``
+              (an alias, nothing is written) and arms the slot with the mask
+              and that tensor; the consumer, finding the slot armed, checks
+              that the gradient it received is that very tensor, applies the
+              mask inside its kernel and disarms the slot. Each backward
+              re-arms, so ``retain_graph=True`` works.
+
+    Anything that replaces or accumulates into the shortcut gradient on the
+    way (a tensor hook, a second use of the shortcut) breaks the contract:
+    the ungated sum cannot be repaired, so ``take`` raises. An unarmed slot
+    changes nothing."""
+
+    __slots__ = ("claimed", "mask", "dy", "version")
+
+    def __init__(self):
+        self.claimed = False
+        self.mask = None
+        self.dy = None
+        self.version = 0
+
+    def claim(self) -> None:
+        self.claimed = True
+
+    @property
+    def armed(self) -> bool:
+        return self.mask is not None
+
+    def arm(self, mask: torch.Tensor, dy: torch.Tensor) -> None:
+        self.mask, self.dy, self.version = mask, dy, dy._version
+
+    def take(self, grad: Optional[torch.Tensor]) -> torch.Tensor:
+        """The mask for ``grad``, which must be the armed tensor; disarms."""
+        mask, dy, version = self.mask, self.dy, self.version
+        self.mask = self.dy = None
+        if (grad is None or grad.data_ptr() != dy.data_ptr()
+                or grad.shape != dy.shape or grad.dtype != dy.dtype
+                or grad.stride() != dy.stride()
+                or grad._version != version):
+            raise RuntimeError(
+                "gated shortcut gradient: the residual join handed its "
+                "output gradient over ungated, to be masked by the op that "
+                "consumes it, but the gradient that arrived is not that "
+                "tensor (a hook or a second use of the shortcut replaced or "
+                "accumulated into it). Set DDLB_GATE=0 to materialise the "
+                "shortcut gradient instead.")
+        return mask
+
+
 # ---------------------------------------------------------------- BN+act
 class _FusedBNAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, res, running_mean, running_var,
-                training, momentum, eps, act_code):
+                training, momentum, eps, act_code, slot=None):
         ext = _ops.require_extension()
         nhwc = _is_nhwc(x)
         x = _layout_contiguous(x, nhwc)
@@ -61,6 +129,19 @@ class _FusedBNAct(torch.autograd.Function):
         ctx.act_code = act_code
         ctx.has_res = res is not None
         ctx.nhwc = nhwc
+        # GateSlot roles: with a residual this BN is the join (producer, if
+        # the consumer claimed the slot and a mask was written); an act-free
+        # BN without one is the downsample BN (consumer, if the masked
+        # kernels cover its tensors)
+        ctx.gate_out = ctx.gate_in = None
+        if slot is not None:
+            if res is not None:
+                if slot.claimed and ctx.masked:
+                    ctx.gate_out = slot
+            elif (act_code == 0 and nhwc and x.dtype == torch.bfloat16
+                  and x.size(1) % 8 == 0):
+                slot.claim()
+                ctx.gate_in = slot
         return y
 
     @staticmethod
@@ -68,12 +149,25 @@ class _FusedBNAct(torch.autograd.Function):
         ext = _ops.require_extension()
         x, mean, invstd, gamma, aux = ctx.saved_tensors
         y, mask = (None, aux) if ctx.masked else (aux, None)
-        out = ext.bn_act_bwd(_layout_contiguous(dy, ctx.nhwc), y, x, mean,
-                             invstd, gamma, ctx.act_code, ctx.training,
-                             ctx.has_res, ctx.nhwc, mask)
+        gate = None
+        if ctx.gate_in is not None and ctx.gate_in.armed:
+            gate = ctx.gate_in.take(dy)
+        dy = _layout_contiguous(dy, ctx.nhwc)
+        # the join hands dy itself on as the shortcut gradient: no dres
+        hand_over = ctx.gate_out is not None
+        out = ext.bn_act_bwd(dy, y, x, mean, invstd, gamma, ctx.act_code,
+                             ctx.training, ctx.has_res and not hand_over,
+                             ctx.nhwc, mask, gate)
         dx, dgamma, dbeta = out[0], out[1], out[2]
-        dres = out[3] if ctx.has_res else None
-        return (dx, dgamma, dbeta, dres, None, None, None, None, None, None)
+        if hand_over:
+            dres = None
+            if ctx.needs_input_grad[3]:
+                ctx.gate_out.arm(mask, dy)
+                dres = dy
+        else:
+            dres = out[3] if ctx.has_res else None
+        return (dx, dgamma, dbeta, dres, None, None, None, None, None, None,
+                None)
 
 
 def bn_act(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
@@ -81,12 +175,15 @@ def bn_act(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
            running_var: Optional[torch.Tensor], training: bool,
            momentum: float = 0.1, eps: float = 1e-5, act: str = "relu",
            res: Optional[torch.Tensor] = None,
-           backend: str = "auto") -> torch.Tensor:
-    """BatchNorm2d + activation (+ residual add), fused on GPU."""
+           backend: str = "auto",
+           gate: Optional[GateSlot] = None) -> torch.Tensor:
+    """BatchNorm2d + activation (+ residual add), fused on GPU. ``gate``
+    is the block's GateSlot: with ``res`` this BN produces the gated
+    shortcut gradient, without it (``act="none"``) it consumes one."""
     if _ops.use_native(x, backend):
         return _FusedBNAct.apply(x, gamma.float(), beta.float(), res,
                                  running_mean, running_var, training,
-                                 momentum, eps, _ACT[act])
+                                 momentum, eps, _ACT[act], gate)
     y = F.batch_norm(x, running_mean, running_var, gamma, beta, training,
                      momentum, eps)
     if res is not None:

@@ -33,7 +33,8 @@ def default_backend() -> str:
 class BNAct(nn.Module):
     """BatchNorm2d + activation (+ optional residual add), fused on GPU.
 
-    forward(x, res=None): y = act(bn(x) + res)
+    forward(x, res=None, gate=None): y = act(bn(x) + res); gate is the
+    block's NF.GateSlot at a residual join (see there).
     Running stats and affine params stay fp32 regardless of model dtype
     (they are re-cast at dispatch; fp32 optimizer-state discipline)."""
 
@@ -69,7 +70,8 @@ class BNAct(nn.Module):
         return self
 
     def forward(self, x: torch.Tensor,
-                res: Optional[torch.Tensor] = None) -> torch.Tensor:
+                res: Optional[torch.Tensor] = None,
+                gate: Optional[NF.GateSlot] = None) -> torch.Tensor:
         if self.training:
             # python-side counter; synced to the buffer on state_dict()
             # (a per-step GPU add showed up as 51 launches/step)
@@ -77,7 +79,7 @@ class BNAct(nn.Module):
         return NF.bn_act(x, self.weight, self.bias, self.running_mean,
                          self.running_var, self.training, self.momentum,
                          self.eps, self.act, res,
-                         backend=_DEFAULT_BACKEND)
+                         backend=_DEFAULT_BACKEND, gate=gate)
 
     def _save_to_state_dict(self, destination, prefix, keep_vars):
         if self._nbt:
