@@ -15,7 +15,11 @@ add it replaces. ``--join`` prints
 only those (plus the plain data-grad) per shape.
 
 ``--stem`` instead times the small-C stem convs the model zoo builds
-(native csrc/conv_stem.hip vs the library), forward and weight-grad."""
+(native csrc/conv_stem.hip vs the library), forward and weight-grad.
+
+``--grouped`` times the seven distinct grouped 3x3 convs of
+resnext50_32x4d (native csrc/conv_grouped.hip vs the library) in all three
+directions, with each direction's share of its byte floor."""
 
 import argparse
 import json
@@ -128,6 +132,71 @@ def bench_stem(args):
         print(json.dumps(res), flush=True)
 
 
+# (C, groups, H/W, stride): the distinct conv2 layers of imagenet
+# resnext50_32x4d
+RESNEXT50_CONV2 = [
+    (128, 32, 56, 1), (256, 32, 56, 2), (256, 32, 28, 1), (512, 32, 28, 2),
+    (512, 32, 14, 1), (1024, 32, 14, 2), (1024, 32, 7, 1),
+]
+
+
+def bench_grouped(args):
+    """Native csrc/conv_grouped.hip against the library, all three
+    directions, alternating in one process; per direction the share of the
+    byte floor (every operand read or written once) the native time is."""
+    from ddlbench_amd.ops import require_extension
+    ext = require_extension()
+    dev = torch.device("cuda", 0)
+    cl = torch.channels_last
+    N = args.batch
+    for C, G, HW, stride in RESNEXT50_CONV2:
+        OHW = (HW + 2 - 3) // stride + 1
+        x = torch.randn(N, C, HW, HW, device=dev,
+                        dtype=torch.bfloat16).contiguous(memory_format=cl)
+        w = torch.randn(C, C // G, 3, 3, device=dev,
+                        dtype=torch.bfloat16).contiguous(memory_format=cl)
+        dy = torch.randn(N, C, OHW, OHW, device=dev,
+                         dtype=torch.bfloat16).contiguous(memory_format=cl)
+
+        def library_bwd(mask):
+            return torch.ops.aten.convolution_backward(
+                dy, x, w, None, [stride, stride], [1, 1], [1, 1], False,
+                [0, 0], G, mask)
+
+        fns = {
+            "native_fwd": lambda: ext.conv_grouped_fwd(x, w, G, stride, 1),
+            "library_fwd": lambda: torch.nn.functional.conv2d(
+                x, w, None, stride, 1, 1, G),
+            "native_dgrad": lambda: ext.conv_grouped_dgrad(
+                dy, w, N, C, HW, HW, G, stride, 1),
+            "library_dgrad": lambda: library_bwd([True, False, False]),
+            "native_wgrad": lambda: ext.conv_grouped_wgrad(
+                x, dy, G, stride, 1),
+            "library_wgrad": lambda: library_bwd([False, True, False]),
+        }
+        res = {"shape": f"C{C}_Cg{C // G}_HW{HW}_s{stride}", "batch": N}
+        # native and library alternate; two passes, the lower time counts
+        best = {}
+        for _ in range(2):
+            for name, fn in fns.items():
+                t = bench_op(fn, args.iters, args.warmup)
+                best[name] = min(best.get(name, t), t)
+        for name, t in best.items():
+            res[name + "_ms"] = round(t * 1e3, 4)
+        floor_bytes = {
+            "fwd": 2 * (x.numel() + w.numel() + dy.numel()),
+            "dgrad": 2 * (dy.numel() + w.numel() + x.numel()),
+            "wgrad": 2 * (x.numel() + dy.numel() + w.numel()),
+        }
+        for d, b in floor_bytes.items():
+            floor = b / (HBM_TBS * 1e12)
+            res[d + "_floor_ms"] = round(floor * 1e3, 4)
+            res[d + "_floor_share"] = round(floor / best["native_" + d], 3)
+            res[d + "_native_over_library"] = round(
+                best["native_" + d] / best["library_" + d], 3)
+        print(json.dumps(res), flush=True)
+
+
 def join_columns(ext, dy, w_perm, x, stride, pad, args):
     """dgrad+add: fused epilogue addend vs dgrad followed by a torch add
     (deep-pipeline structure; g stands in for the shortcut's gradient)."""
@@ -162,6 +231,9 @@ def main():
     p.add_argument("--stem", action="store_true",
                    help="time the model zoo's stem convs (native vs "
                         "library, forward and weight-grad) instead")
+    p.add_argument("--grouped", action="store_true",
+                   help="time the grouped 3x3 convs of resnext50_32x4d "
+                        "(native vs library, fwd/dgrad/wgrad) instead")
     p.add_argument("--join", action="store_true",
                    help="per shape, only the data-grad and the dgrad+add "
                         "columns (fused addend vs dgrad then torch add)")
@@ -170,6 +242,9 @@ def main():
     torch.backends.cudnn.benchmark = True
     if args.stem:
         bench_stem(args)
+        return
+    if args.grouped:
+        bench_grouped(args)
         return
     from ddlbench_amd.ops.conv import conv2d_mfma
     dev = torch.device("cuda", 0)

@@ -10,7 +10,12 @@ Eligibility: bf16, channels_last, groups=1, dilation=1, C%8==0, K%8==0.
 Stem convs (C < 8) stay on the library path by default; with
 ``DDLB_STEM=native`` (or ``convert_convs(model, stem="native")``) they run
 the small-C kernels of csrc/conv_stem.hip (forward + weight-grad) through
-``Conv2dStem``."""
+``Conv2dStem``.
+
+Grouped 3x3 convs (ResNeXt's conv2) likewise stay on the library by
+default; ``DDLB_GROUPED=native`` (or ``convert_convs(model,
+grouped="native")``) runs the forward, data-grad and weight-grad kernels of
+csrc/conv_grouped.hip through ``Conv2dGrouped``."""
 
 from __future__ import annotations
 
@@ -289,8 +294,95 @@ class Conv2dStem(_NativeConv2d):
         return conv2d_stem(x, self.weight, self.stride, self.padding)
 
 
+class _ConvGrouped(torch.autograd.Function):
+    """Grouped 3x3 conv on the kernels of csrc/conv_grouped.hip: forward,
+    data-grad and weight-grad (bf16, in the weight's layout), each
+    backward direction only when its gradient is needed."""
+
+    @staticmethod
+    def forward(ctx, x, weight, groups, stride, pad):
+        ext = _ops.require_extension()
+        x = x.contiguous(memory_format=_CL)
+        w = weight.contiguous(memory_format=_CL)
+        y = ext.conv_grouped_fwd(x, w, groups, stride, pad)
+        ctx.save_for_backward(x, weight)
+        ctx.groups = groups
+        ctx.stride = stride
+        ctx.pad = pad
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        ext = _ops.require_extension()
+        x, weight = ctx.saved_tensors
+        dy = dy.contiguous(memory_format=_CL)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = ext.conv_grouped_dgrad(
+                dy, weight.contiguous(memory_format=_CL), x.size(0),
+                x.size(1), x.size(2), x.size(3), ctx.groups, ctx.stride,
+                ctx.pad)
+        if ctx.needs_input_grad[1]:
+            dw = ext.conv_grouped_wgrad(x, dy, ctx.groups, ctx.stride,
+                                        ctx.pad)
+        return dx, dw, None, None, None
+
+
+def conv2d_grouped(x, weight, groups, stride=1, pad=0):
+    return _ConvGrouped.apply(x, weight, groups, stride, pad)
+
+
+def grouped_eligible(conv: nn.Conv2d, x_dtype=torch.bfloat16) -> bool:
+    """True for the problems csrc/conv_grouped.hip supports: groups > 1,
+    as many output as input channels, C/groups in {4, 8, 16, 32}, C a
+    multiple of 16 (32 for C/groups = 32), 3x3, stride 1 or 2, pad 0 or 1,
+    dilation 1, no bias."""
+    cg = conv.in_channels // conv.groups
+    return (x_dtype == torch.bfloat16
+            and conv.groups > 1
+            and conv.in_channels == conv.out_channels
+            and cg in (4, 8, 16, 32)
+            and conv.in_channels % (32 if cg == 32 else 16) == 0
+            and conv.dilation == (1, 1)
+            and conv.bias is None
+            and conv.kernel_size == (3, 3)
+            and conv.stride in ((1, 1), (2, 2))
+            and conv.padding in ((0, 0), (1, 1)))
+
+
+class Conv2dGrouped(_NativeConv2d):
+    """Drop-in for a grouped_eligible nn.Conv2d, running the grouped
+    kernels."""
+
+    tag = "grouped"
+
+    def __init__(self, conv: nn.Conv2d):
+        super().__init__(conv)
+        self.groups = conv.groups
+
+    def native(self, x):
+        return conv2d_grouped(x, self.weight, self.groups, self.stride,
+                              self.padding)
+
+    def forward(self, x):
+        if x.is_cuda and x.dtype == torch.bfloat16:
+            return self.native(x)
+        return F.conv2d(x, self.weight, None, self.stride, self.padding,
+                        1, self.groups)
+
+
+def _mode(value, env, what):
+    """A "native"/"library" switch; None reads the environment variable."""
+    if value is None:
+        value = os.environ.get(env, "library")
+    if value not in ("native", "library"):
+        raise ValueError(
+            f"{what} must be 'native' or 'library', got {value!r}")
+    return value
+
+
 def convert_convs(model: nn.Module, dtype=torch.bfloat16,
-                  stem=None) -> int:
+                  stem=None, grouped=None) -> int:
     """Replace eligible nn.Conv2d children with Conv2dMFMA and eligible
     nn.MaxPool2d with the native NHWC pool. Returns the number of
     conversions.
@@ -298,11 +390,10 @@ def convert_convs(model: nn.Module, dtype=torch.bfloat16,
     ``stem`` selects the path of small-C stem convs: "library" (default)
     leaves them as nn.Conv2d, "native" swaps stem_eligible ones for
     Conv2dStem and counts them. ``stem=None`` reads DDLB_STEM at call
-    time."""
-    if stem is None:
-        stem = os.environ.get("DDLB_STEM", "library")
-    if stem not in ("native", "library"):
-        raise ValueError(f"stem must be 'native' or 'library', got {stem!r}")
+    time. ``grouped`` does the same for grouped_eligible 3x3 convs
+    (Conv2dGrouped, DDLB_GROUPED)."""
+    stem = _mode(stem, "DDLB_STEM", "stem")
+    grouped = _mode(grouped, "DDLB_GROUPED", "grouped")
     count = 0
     for parent in model.modules():
         for name, child in list(parent.named_children()):
@@ -313,6 +404,9 @@ def convert_convs(model: nn.Module, dtype=torch.bfloat16,
                 count += 1
             elif stem == "native" and stem_eligible(child, dtype):
                 setattr(parent, name, Conv2dStem(child))
+                count += 1
+            elif grouped == "native" and grouped_eligible(child, dtype):
+                setattr(parent, name, Conv2dGrouped(child))
                 count += 1
     if dtype == torch.bfloat16 and \
             os.environ.get("DDLB_MAXPOOL", "1") != "0":

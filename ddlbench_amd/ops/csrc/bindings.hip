@@ -974,6 +974,103 @@ torch::Tensor conv_stem_wgrad(torch::Tensor x, torch::Tensor dy, int64_t R,
   return dw;
 }
 
+// ---- grouped 3x3 conv (NHWC bf16) -------------------------------------
+// Supported problem of csrc/conv_grouped.hip; a violation raises before
+// any launch. Returns Cg.
+static int check_grouped_shape(int64_t C, int64_t K, int64_t groups,
+                               int64_t stride, int64_t pad) {
+  TORCH_CHECK(groups > 1 && C == K && C % groups == 0,
+              "conv_grouped needs groups > 1 dividing C, and C == K");
+  const int64_t Cg = C / groups;
+  TORCH_CHECK(Cg == 4 || Cg == 8 || Cg == 16 || Cg == 32,
+              "conv_grouped needs C/groups in {4, 8, 16, 32}");
+  TORCH_CHECK(C % (Cg == 32 ? 32 : 16) == 0,
+              "conv_grouped needs C % 16 == 0");
+  TORCH_CHECK(stride == 1 || stride == 2, "conv_grouped needs stride 1 or 2");
+  TORCH_CHECK(pad == 0 || pad == 1, "conv_grouped needs pad 0 or 1");
+  return (int)Cg;
+}
+
+static void check_grouped_weight(const torch::Tensor& w,
+                                 const torch::Tensor& like, int64_t C,
+                                 int64_t Cg) {
+  check_conv_operand(w, "w", "conv_grouped");
+  TORCH_CHECK(w.device() == like.device(),
+              "conv_grouped: w must be on the input's device");
+  TORCH_CHECK(w.dim() == 4 && w.size(0) == C && w.size(1) == Cg &&
+                  w.size(2) == 3 && w.size(3) == 3,
+              "conv_grouped: w must be (C, C/groups, 3, 3)");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
+              "conv_grouped: w must be 16-byte aligned");
+}
+
+// x: (N,C,H,W) channels_last; w: (C,Cg,3,3) channels_last. Returns
+// channels_last y.
+torch::Tensor conv_grouped_fwd(torch::Tensor x, torch::Tensor w,
+                               int64_t groups, int64_t stride, int64_t pad) {
+  TORCH_CHECK(x.dim() == 4 && w.dim() == 4, "conv_grouped: 4-D tensors only");
+  check_conv_operand(x, "x", "conv_grouped");
+  const int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  const int Cg = check_grouped_shape(C, w.size(0), groups, stride, pad);
+  check_grouped_weight(w, x, C, Cg);
+  check_conv_geometry("conv_grouped", N, H, W, 3, 3, stride, pad);
+  const int OH = conv_out_size(H, pad, 3, stride);
+  const int OW = conv_out_size(W, pad, 3, stride);
+  auto y = empty_nhwc(x, N, C, OH, OW);
+  launch_conv_grouped_fwd(x.data_ptr(), w.data_ptr(), y.data_ptr(), N, H, W,
+                          C, Cg, OH, OW, (int)stride, (int)pad, cur_stream());
+  return y;
+}
+
+// dy: (N,C,OH,OW) channels_last; w as in the forward (the kernel reads it
+// flipped and transposed itself). Returns channels_last dx (N,C,H,W).
+torch::Tensor conv_grouped_dgrad(torch::Tensor dy, torch::Tensor w,
+                                 int64_t N, int64_t C, int64_t H, int64_t W,
+                                 int64_t groups, int64_t stride,
+                                 int64_t pad) {
+  TORCH_CHECK(dy.dim() == 4 && w.dim() == 4, "conv_grouped: 4-D tensors only");
+  check_conv_operand(dy, "dy", "conv_grouped");
+  const int Cg = check_grouped_shape(C, dy.size(1), groups, stride, pad);
+  check_grouped_weight(w, dy, C, Cg);
+  check_conv_geometry("conv_grouped", N, H, W, 3, 3, stride, pad);
+  check_conv_dy("conv_grouped", dy, N, H, W, 3, 3, stride, pad);
+  auto dx = empty_nhwc(dy, N, C, H, W);
+  launch_conv_grouped_dgrad(dy.data_ptr(), w.data_ptr(), dx.data_ptr(),
+                            (int)N, (int)H, (int)W, (int)C, Cg,
+                            (int)dy.size(2), (int)dy.size(3), (int)stride,
+                            (int)pad, cur_stream());
+  return dx;
+}
+
+// x: (N,C,H,W) channels_last; dy: (N,C,OH,OW) channels_last. Returns bf16
+// dw of logical shape (C,Cg,3,3) with channels_last strides, each element
+// the round-to-nearest-even bf16 of its fp32 sum.
+torch::Tensor conv_grouped_wgrad(torch::Tensor x, torch::Tensor dy,
+                                 int64_t groups, int64_t stride,
+                                 int64_t pad) {
+  TORCH_CHECK(x.dim() == 4 && dy.dim() == 4, "conv_grouped: 4-D tensors only");
+  check_conv_operand(x, "x", "conv_grouped");
+  check_conv_operand(dy, "dy", "conv_grouped");
+  TORCH_CHECK(dy.device() == x.device(),
+              "conv_grouped: dy must be on x's device");
+  const int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  const int Cg = check_grouped_shape(C, dy.size(1), groups, stride, pad);
+  check_conv_geometry("conv_grouped", N, H, W, 3, 3, stride, pad);
+  check_conv_dy("conv_grouped", dy, N, H, W, 3, 3, stride, pad);
+  const int OH = dy.size(2), OW = dy.size(3);
+  auto dw = torch::empty({C, 3, 3, Cg}, x.options()).permute({0, 3, 1, 2});
+  // per-block partial slabs, grown to need; every slab element the
+  // combine reads is written by the same call
+  static WsCache gws;
+  auto part = cached_ws(gws, x, at::kFloat,
+                        conv_grouped_wgrad_part_floats(N, C, Cg, OH, OW,
+                                                       (int)stride));
+  launch_conv_grouped_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr(),
+                            part.data_ptr<float>(), N, H, W, C, Cg, OH, OW,
+                            (int)stride, (int)pad, cur_stream());
+  return dw;
+}
+
 // ---- NHWC max-pool ----------------------------------------------------
 std::vector<torch::Tensor> maxpool_fwd(torch::Tensor x, int64_t k,
                                        int64_t stride, int64_t pad) {
@@ -1135,6 +1232,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "NHWC bf16 MFMA stem conv (C < 8) forward");
   m.def("conv_stem_wgrad", &conv_stem_wgrad,
         "NHWC bf16 MFMA stem conv (C < 8) weight-grad (fp32 out)");
+  m.def("conv_grouped_fwd", &conv_grouped_fwd,
+        "NHWC bf16 MFMA grouped 3x3 conv forward");
+  m.def("conv_grouped_dgrad", &conv_grouped_dgrad,
+        "NHWC bf16 MFMA grouped 3x3 conv data-grad");
+  m.def("conv_grouped_wgrad", &conv_grouped_wgrad,
+        "NHWC bf16 MFMA grouped 3x3 conv weight-grad (bf16 out, the "
+        "weight's layout)");
   m.def("ce_fwd", &ce_fwd, "cross-entropy forward");
   m.def("ce_bwd", &ce_bwd, "cross-entropy backward");
   m.def("ls_ce_fwd", &ls_ce_fwd,

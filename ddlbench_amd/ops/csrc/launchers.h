@@ -207,6 +207,24 @@ void launch_conv_stem_wgrad(const void* x, const void* dy, float* dw,
                             hipStream_t stream);
 int conv_stem_wgrad_chunks(int N, int OH, int OW, int K);
 
+// ---- conv_grouped.hip: 3x3 grouped conv, C in == C out, Cg = C/groups
+// in {4, 8, 16, 32}, stride 1 or 2, pad 0 or 1 (anything else throws).
+// H, W are x's and OH, OW y's in all three; w and dw are (C,3,3,Cg) bf16 --
+void launch_conv_grouped_fwd(const void* x, const void* w, void* y, int N,
+                             int H, int W, int C, int Cg, int OH, int OW,
+                             int stride, int pad, hipStream_t stream);
+void launch_conv_grouped_dgrad(const void* dy, const void* w, void* dx,
+                               int N, int H, int W, int C, int Cg, int OH,
+                               int OW, int stride, int pad,
+                               hipStream_t stream);
+// part: conv_grouped_wgrad_part_floats(...) floats of slab workspace
+void launch_conv_grouped_wgrad(const void* x, const void* dy, void* dw,
+                               float* part, int N, int H, int W, int C,
+                               int Cg, int OH, int OW, int stride, int pad,
+                               hipStream_t stream);
+long conv_grouped_wgrad_part_floats(int N, int C, int Cg, int OH, int OW,
+                                    int stride);
+
 // ---- maxpool.hip ------------------------------------------------------
 void launch_maxpool_fwd(const void*, void*, unsigned char*, int64_t,
                         int64_t, int, int, int, int, int, int, int,

@@ -26,6 +26,7 @@ KERNEL_SOURCES = [
     "attn_score.hip",
     "bindings.hip",
     "bn_act.hip",
+    "conv_grouped.hip",
     "conv_mfma.hip",
     "conv_mfma2.hip",
     "conv_stem.hip",
