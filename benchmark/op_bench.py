@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Fused-op microbenchmarks vs eager PyTorch: BN+ReLU(+add), CE,
-label-smoothed CE, attention score, LSTM, SGD (--ops picks arms).
+label-smoothed CE, attention score, attention context, LSTM, SGD (--ops
+picks arms).
 
 Reports ms and achieved HBM GB/s per op over ResNet-50 activation
 shapes in both layouts — the evidence for the memory-bound fusion wins
@@ -160,6 +161,79 @@ def bench_attn(dev, iters, warmup, rounds=5):
         del q, k, ds, leaves
 
 
+def bench_attn_ctx(dev, iters, warmup, rounds=5):
+    """Attention softmax + context, bf16, H = 1024, about a fifth of the keys
+    masked through per-sentence lengths: NF.attention_context(native)
+    against the two eager lines of the attention module (fp32 softmax over
+    the -65504-filled scores, then bmm), alternated in rounds in one
+    process. Training shapes run forward + backward through autograd with
+    gradients to the scores and the values; the decode shape (Tq = 1) runs
+    forward only under no_grad."""
+    from ddlbench_amd.ops import functional as NF
+    H = 1024
+    dt = torch.bfloat16
+    for B, Tq, Tk, train in ((64, 32, 32, True), (128, 50, 50, True),
+                             (64, 1, 50, False)):
+        g = torch.Generator(device=dev).manual_seed(B * Tk + 1)
+        mk = lambda *s: torch.randn(*s, device=dev, dtype=dt, generator=g)
+        lengths = (Tk * (0.6 + 0.4 * torch.rand(B, device=dev, generator=g))
+                   ).round().long().clamp(1, Tk)
+        mask = torch.arange(Tk, device=dev).unsqueeze(0) \
+            < lengths.unsqueeze(1)
+        scores = mk(B, Tq, Tk).masked_fill(~mask.unsqueeze(1),
+                                           NF.MASKED_SCORE)
+        # (Tk, B, H) memory, as the decoder hands the encoder output over
+        values = mk(Tk, B, H).transpose(0, 1)
+        dctx = mk(B, Tq, H)
+        leaves = [t.requires_grad_(train) for t in (scores, values)]
+
+        def op(backend):
+            if backend == "native":
+                return NF.attention_context(*leaves, mask, backend="native")
+            attn = torch.softmax(leaves[0].float(), dim=-1).to(dt)
+            return torch.bmm(attn, leaves[1]), attn
+
+        def step(backend):
+            if not train:
+                with torch.no_grad():
+                    op(backend)
+                return
+            for t in leaves:
+                t.grad = None
+            op(backend)[0].backward(dctx)
+
+        times = {"native": [], "eager": []}
+        peak = {}
+        for backend in times:
+            step(backend)
+            for t in leaves:
+                t.grad = None
+            torch.cuda.synchronize()
+            base = torch.cuda.memory_allocated()
+            torch.cuda.reset_peak_memory_stats()
+            step(backend)
+            torch.cuda.synchronize()
+            # beyond the inputs: outputs and gradients are part of each arm
+            peak[backend] = torch.cuda.max_memory_allocated() - base
+        for _ in range(rounds):
+            for backend in times:
+                times[backend].append(
+                    timeit(lambda: step(backend), iters, warmup))
+        med = {b: sorted(v)[len(v) // 2] for b, v in times.items()}
+        print(json.dumps({
+            "op": "attn_ctx_fwd_bwd" if train else "attn_ctx_fwd",
+            "shape": f"B{B} Tq{Tq} Tk{Tk} H{H}", "dtype": "bfloat16",
+            "valid_keys": int(mask.sum()),
+            "native_ms": round(med["native"] * 1e3, 4),
+            "native_ms_min": round(min(times["native"]) * 1e3, 4),
+            "eager_ms": round(med["eager"] * 1e3, 4),
+            "eager_ms_min": round(min(times["eager"]) * 1e3, 4),
+            "speedup": round(med["eager"] / med["native"], 2),
+            "native_peak_MB": round(peak["native"] / 2**20, 2),
+            "eager_peak_MB": round(peak["eager"] / 2**20, 2)}), flush=True)
+        del scores, values, dctx, leaves
+
+
 def bench_lstm(dev, iters, warmup, rounds=5):
     """One single-layer bf16 LSTM, the native recurrence against the library
     path (ops.modules.LSTM backend "native" / "library"), alternated in
@@ -226,12 +300,13 @@ def main():
     p.add_argument("--iters", type=int, default=20)
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--dtype", default="bfloat16")
-    p.add_argument("--ops", default="bn,ce,ls_ce,attn,lstm,sgd",
-                   help="comma-separated arms: bn, ce, ls_ce, attn, lstm, "
-                        "sgd")
+    p.add_argument("--ops", default="bn,ce,ls_ce,attn,attn_ctx,lstm,sgd",
+                   help="comma-separated arms: bn, ce, ls_ce, attn, "
+                        "attn_ctx, lstm, sgd")
     args = p.parse_args()
     arms = set(args.ops.split(","))
-    assert arms <= {"bn", "ce", "ls_ce", "attn", "lstm", "sgd"}, args.ops
+    assert arms <= {"bn", "ce", "ls_ce", "attn", "attn_ctx", "lstm",
+                    "sgd"}, args.ops
     assert torch.cuda.is_available()
     from ddlbench_amd.ops import functional as NF
     dev = torch.device("cuda", 0)
@@ -329,6 +404,8 @@ def main():
 
     if "attn" in arms:
         bench_attn(dev, args.iters, args.warmup)
+    if "attn_ctx" in arms:
+        bench_attn_ctx(dev, args.iters, args.warmup)
 
     if "lstm" in arms:
         bench_lstm(dev, args.iters, args.warmup)

@@ -121,10 +121,13 @@ class BahdanauAttention(nn.Module):
     """Normalized additive attention (reference attention.py:12-115).
     The score runs the fused native kernels on a GPU and the torch
     composition on CPU; ``backend`` ("auto", "native", "torch") or, while it
-    is "auto", DDLB_ATTN_SCORE picks one explicitly."""
+    is "auto", DDLB_ATTN_SCORE picks one explicitly. The softmax and the
+    context product are the library composition by default ("library");
+    ``ctx_backend`` or, while it is "auto", DDLB_ATTN_CTX set to "native"
+    or "torch" sends them through ``NF.attention_context``."""
 
     def __init__(self, query_size: int, key_size: int, hidden: int,
-                 backend: str = "auto"):
+                 backend: str = "auto", ctx_backend: str = "auto"):
         super().__init__()
         self.linear_q = nn.Linear(query_size, hidden, bias=False)
         self.linear_k = nn.Linear(key_size, hidden, bias=False)
@@ -134,6 +137,17 @@ class BahdanauAttention(nn.Module):
         nn.init.uniform_(self.v, -1.0 / math.sqrt(hidden),
                          1.0 / math.sqrt(hidden))
         self.backend = backend
+        self.ctx_backend = ctx_backend
+
+    def resolve_ctx_backend(self) -> str:
+        """As resolve_backend, for the softmax and context product."""
+        backend = self.ctx_backend
+        if backend == "auto":
+            backend = os.environ.get("DDLB_ATTN_CTX", "library")
+        if backend not in ("library", "native", "torch"):
+            raise ValueError("attention context backend must be library, "
+                             f"native or torch, got {backend!r}")
+        return backend
 
     def resolve_backend(self) -> str:
         """The backend the next forward uses; the environment is read here,
@@ -157,6 +171,9 @@ class BahdanauAttention(nn.Module):
         q = self.linear_q(query)
         k = self.linear_k(keys)
         scores = self.score(q, k, mask)
+        ctx_backend = self.resolve_ctx_backend()
+        if ctx_backend != "library":
+            return NF.attention_context(scores, keys, mask, ctx_backend)
         attn = F.softmax(scores.float(), dim=-1).to(keys.dtype)
         ctx = torch.bmm(attn, keys)
         return ctx, attn

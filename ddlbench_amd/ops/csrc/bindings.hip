@@ -557,6 +557,110 @@ std::vector<torch::Tensor> attn_score_bwd(torch::Tensor ds, torch::Tensor q,
   return {dq, dk, dbias, dvn};
 }
 
+// ---- fused attention softmax + context ---------------------------------
+// Shared checks of scores (B,Tq,Tk), values (B,Tk,H; any batch and key
+// stride, h stride 1) and mask; returns the mask's data pointer.
+const uint8_t* check_attn_ctx(const torch::Tensor& like,
+                              const torch::Tensor& values,
+                              const c10::optional<torch::Tensor>& mask) {
+  TORCH_CHECK(like.is_cuda() && values.is_cuda(),
+              "attn_ctx: tensors must be on the HIP device");
+  TORCH_CHECK(like.scalar_type() == at::kFloat || is_bf16(like),
+              "attn_ctx: tensors must be fp32 or bf16");
+  TORCH_CHECK(values.scalar_type() == like.scalar_type(),
+              "attn_ctx: all tensors must share one dtype");
+  TORCH_CHECK(values.device() == like.device(),
+              "attn_ctx: all tensors must be on one device");
+  TORCH_CHECK(like.dim() == 3 && like.is_contiguous(),
+              "attn_ctx: scores / attn must be contiguous (B, Tq, Tk)");
+  const int64_t B = like.size(0), Tq = like.size(1), Tk = like.size(2);
+  TORCH_CHECK(B >= 1 && Tq >= 1 && Tk >= 1,
+              "attn_ctx: B, Tq and Tk must be at least 1");
+  TORCH_CHECK(values.dim() == 3 && values.size(0) == B &&
+                  values.size(1) == Tk && values.size(2) >= 1,
+              "attn_ctx: values must be (B, Tk, H) with the scores' B and Tk");
+  TORCH_CHECK(values.stride(2) == 1,
+              "attn_ctx: values must have h stride 1");
+  TORCH_CHECK(Tk <= kAttnCtxMaxTk, "attn_ctx: Tk = ", Tk,
+              " is over the cap of ", kAttnCtxMaxTk, " keys");
+  const int64_t H = values.size(2);
+  TORCH_CHECK(B * std::max((Tq + 15) / 16 * 16,
+                           ((Tk + 15) / 16) * ((H + 255) / 256)) <
+                  (1LL << 31),
+              "attn_ctx: too many blocks for one launch");
+  if (!mask.has_value()) return nullptr;
+  const torch::Tensor& m = *mask;
+  check_gpu_contig(m, "mask");
+  TORCH_CHECK(m.scalar_type() == at::kBool || m.scalar_type() == at::kByte,
+              "attn_ctx: mask must be bool or uint8");
+  TORCH_CHECK(m.device() == like.device(),
+              "attn_ctx: mask must be on the scores' device");
+  TORCH_CHECK(m.dim() == 2 && m.size(0) == B && m.size(1) == Tk,
+              "attn_ctx: mask must be (B, Tk)");
+  return reinterpret_cast<const uint8_t*>(m.data_ptr());
+}
+
+// -> {ctx, attn}
+std::vector<torch::Tensor> attn_ctx_fwd(torch::Tensor scores,
+                                        torch::Tensor values,
+                                        c10::optional<torch::Tensor> mask) {
+  const uint8_t* mp = check_attn_ctx(scores, values, mask);
+  const int64_t B = scores.size(0), Tq = scores.size(1), Tk = scores.size(2),
+                H = values.size(2);
+  torch::Tensor attn = torch::empty_like(scores);
+  torch::Tensor ctx = torch::empty({B, Tq, H}, scores.options());
+  auto s = cur_stream();
+  dispatch_f32_bf16(scores, [&](auto tag) {
+    using T = decltype(tag);
+    launch_attn_ctx_fwd<T>(dptr<T>(scores), dptr<T>(values), mp,
+                           dptr<T>(attn), dptr<T>(ctx), B, Tq, Tk, H,
+                           values.stride(0), values.stride(1), s);
+  });
+  return {ctx, attn};
+}
+
+// -> {dscores, dvalues}; what is not needed comes back undefined and its
+// kernel does not run. dctx is (B, Tq, H) with h stride 1.
+std::vector<torch::Tensor> attn_ctx_bwd(torch::Tensor dctx,
+                                        c10::optional<torch::Tensor> dattn,
+                                        torch::Tensor attn,
+                                        torch::Tensor values,
+                                        c10::optional<torch::Tensor> mask,
+                                        bool need_scores, bool need_values) {
+  const uint8_t* mp = check_attn_ctx(attn, values, mask);
+  const int64_t B = attn.size(0), Tq = attn.size(1), Tk = attn.size(2),
+                H = values.size(2);
+  TORCH_CHECK(dctx.is_cuda() && dctx.scalar_type() == attn.scalar_type() &&
+                  dctx.device() == attn.device(),
+              "attn_ctx_bwd: dctx must have attn's dtype and device");
+  TORCH_CHECK(dctx.dim() == 3 && dctx.size(0) == B && dctx.size(1) == Tq &&
+                  dctx.size(2) == H,
+              "attn_ctx_bwd: dctx must be (B, Tq, H)");
+  TORCH_CHECK(dctx.stride(2) == 1, "attn_ctx_bwd: dctx must have h stride 1");
+  if (dattn.has_value()) {
+    TORCH_CHECK(dattn->is_cuda() && dattn->is_contiguous() &&
+                    dattn->scalar_type() == attn.scalar_type() &&
+                    dattn->device() == attn.device() &&
+                    dattn->sizes() == attn.sizes(),
+                "attn_ctx_bwd: dattn must be contiguous with attn's shape, "
+                "dtype and device");
+  }
+  torch::Tensor ds, dv;
+  if (need_scores) ds = torch::empty_like(attn);
+  if (need_values) dv = torch::empty({B, Tk, H}, attn.options());
+  auto s = cur_stream();
+  dispatch_f32_bf16(attn, [&](auto tag) {
+    using T = decltype(tag);
+    launch_attn_ctx_bwd<T>(
+        dptr<T>(dctx), dattn.has_value() ? dptr<T>(*dattn) : nullptr,
+        dptr<T>(attn), dptr<T>(values), mp,
+        ds.defined() ? dptr<T>(ds) : nullptr,
+        dv.defined() ? dptr<T>(dv) : nullptr, B, Tq, Tk, H, values.stride(0),
+        values.stride(1), dctx.stride(0), dctx.stride(1), s);
+  });
+  return {ds, dv};
+}
+
 // ---- LSTM recurrence ----------------------------------------------------
 // Shape, dtype, device and alignment of one tensor the step kernels read or
 // write; bf16 rows are fetched as 16-byte fragments.
@@ -1253,6 +1357,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("ds"), py::arg("q"), py::arg("k"), py::arg("bias"),
         py::arg("vn"), py::arg("mask") = py::none(),
         py::arg("need_q") = true, py::arg("need_k") = true);
+  m.def("attn_ctx_fwd", &attn_ctx_fwd,
+        "fused attention softmax + context forward -> ctx, attn",
+        py::arg("scores"), py::arg("values"), py::arg("mask") = py::none());
+  m.def("attn_ctx_bwd", &attn_ctx_bwd,
+        "fused attention softmax + context backward -> dscores, dvalues",
+        py::arg("dctx"), py::arg("dattn"), py::arg("attn"),
+        py::arg("values"), py::arg("mask") = py::none(),
+        py::arg("need_scores") = true, py::arg("need_values") = true);
   m.def("lstm_fwd", &lstm_fwd,
         "LSTM recurrence forward: one native kernel per time step");
   m.def("lstm_bwd", &lstm_bwd,

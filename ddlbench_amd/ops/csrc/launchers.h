@@ -124,6 +124,29 @@ void launch_attn_score_bwd(const T* ds, const T* q, const T* k,
                            int64_t B, int64_t Tq, int64_t Tk, int64_t H,
                            int need_q, int need_k, hipStream_t);
 
+// ---- attn_ctx.hip -----------------------------------------------------
+// attn[b,i,:] = softmax over valid keys of scores[b,i,:], ctx = attn values,
+// for dense scores / attn (B,Tq,Tk) and values (B,Tk,H) with batch stride
+// vsb, key stride vsj (in elements) and h stride 1; ctx is dense (B,Tq,H).
+// mask (B,Tk), 1 = valid key, nullptr = none; a masked key's score and
+// values row are never read. Tk <= kAttnCtxMaxTk (throws above it);
+// B * max(ceil(Tq / 16), Tk's tiles * ceil(H / 256)) < 2^31.
+constexpr int kAttnCtxMaxTk = 1024;
+template <typename T>
+void launch_attn_ctx_fwd(const T* scores, const T* values,
+                         const uint8_t* mask, T* attn, T* ctx, int64_t B,
+                         int64_t Tq, int64_t Tk, int64_t H, int64_t vsb,
+                         int64_t vsj, hipStream_t);
+// dctx is (B,Tq,H) with batch stride dsb, row stride dsi and h stride 1;
+// dattn (dense, like attn) may be nullptr. dscores (B,Tq,Tk) and dvalues
+// (B,Tk,H) are dense; a nullptr output skips the kernel that makes it.
+template <typename T>
+void launch_attn_ctx_bwd(const T* dctx, const T* dattn, const T* attn,
+                         const T* values, const uint8_t* mask, T* dscores,
+                         T* dvalues, int64_t B, int64_t Tq, int64_t Tk,
+                         int64_t H, int64_t vsb, int64_t vsj, int64_t dsb,
+                         int64_t dsi, hipStream_t);
+
 // ---- conv_mfma.hip: forward (dgrad=0) or data-grad (dgrad=1); the dims
 // are always those of the forward conv. add (dgrad only, nullptr = none)
 // is a read-only bf16 tensor of dx's geometry summed into dx in the

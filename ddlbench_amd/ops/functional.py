@@ -334,6 +334,101 @@ def attention_score(q: torch.Tensor, k: torch.Tensor, bias: torch.Tensor,
     return scores
 
 
+# ------------------------------------- attention softmax and context
+ATTN_CTX_MAX_TK = 1024
+
+
+class _FusedAttnCtx(torch.autograd.Function):
+    """Saves attn (output dtype), values and the mask: no fp32 scores or
+    probabilities outlive the forward kernel."""
+
+    @staticmethod
+    def forward(ctx, scores, values, mask):
+        ext = _ops.require_extension()
+        out, attn = ext.attn_ctx_fwd(scores, values, mask)
+        ctx.save_for_backward(attn, values, mask)
+        ctx.set_materialize_grads(False)
+        return out, attn
+
+    @staticmethod
+    def backward(ctx, dctx, dattn):
+        ext = _ops.require_extension()
+        attn, values, mask = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        if dctx is None:
+            dctx = torch.zeros_like(values[:, :1]).expand(
+                attn.size(0), attn.size(1), values.size(2))
+        elif dctx.stride(2) != 1:
+            dctx = dctx.contiguous()
+        if dattn is not None:
+            dattn = dattn.contiguous()
+        ds, dv = ext.attn_ctx_bwd(dctx, dattn, attn, values, mask,
+                                  need[0], need[1])
+        return ds, dv, None
+
+
+def _attn_ctx_native_reject(scores, values) -> Optional[str]:
+    """Why the native kernels cannot run these tensors, or None."""
+    if scores.device.type != "cuda":
+        return f"a {scores.device.type} tensor (the kernels are HIP only)"
+    if scores.dim() == 3 and scores.size(2) > ATTN_CTX_MAX_TK:
+        return (f"Tk = {scores.size(2)} (the cap is {ATTN_CTX_MAX_TK}: the "
+                "16-row probability tile must fit in 64 KiB of LDS)")
+    return None
+
+
+def attention_context(scores: torch.Tensor, values: torch.Tensor,
+                      mask: Optional[torch.Tensor] = None,
+                      backend: str = "auto"):
+    """``attn = softmax(scores)`` over the valid keys and ``ctx = attn @
+    values`` for scores (B, Tq, Tk) and values (B, Tk, H), fp32 or bf16, as
+    ``(ctx, attn)`` in the inputs' dtype. ``mask`` is (B, Tk) bool, True for
+    a valid key, in any pattern. A masked key has ``attn == 0`` exactly and
+    takes no gradient; its score and its values row are never read. ctx is
+    computed from attn as returned (rounded to the output dtype).
+
+    A row with no valid key gives ``attn = 0`` and ``ctx = 0``. (The lines
+    this replaces in ``BahdanauAttention``, a softmax over scores filled
+    with -65504, give a uniform row there.)
+
+    ``values`` may be strided in its first two dimensions (h stride 1): the
+    native path reads it in place. Above ``ATTN_CTX_MAX_TK`` keys "auto"
+    takes the torch composition and "native" raises."""
+    if backend not in ("auto", "native", "torch"):
+        raise ValueError("attention_context backend must be auto, native or "
+                         f"torch, got {backend!r}")
+    native = _ops.use_native(scores, backend)
+    if native:
+        why = _attn_ctx_native_reject(scores, values)
+        if why is not None:
+            if backend == "native":
+                raise NotImplementedError(
+                    f"native attention_context does not support {why}; pass "
+                    "backend=\"torch\" for the composition")
+            native = False
+    if native:
+        scores = scores.contiguous()
+        if values.dim() == 3 and values.stride(2) != 1:
+            values = values.contiguous()
+        if mask is not None:
+            mask = mask.contiguous()
+        if torch.is_grad_enabled() and (scores.requires_grad
+                                        or values.requires_grad):
+            return _FusedAttnCtx.apply(scores, values, mask)
+        # nothing to differentiate (greedy / beam decode): keep nothing
+        out, attn = _ops.require_extension().attn_ctx_fwd(
+            scores.detach(), values.detach(), mask)
+        return out, attn
+    s = scores.float()
+    if mask is not None:
+        s = s.masked_fill(~mask.unsqueeze(1), float("-inf"))
+    attn = torch.nan_to_num(F.softmax(s, dim=-1), nan=0.0).to(values.dtype)
+    if mask is not None:
+        # a masked values row may hold anything: it is not read
+        values = values.masked_fill(~mask.unsqueeze(2), 0)
+    return torch.bmm(attn, values), attn
+
+
 # ------------------------------------------------------------------ LSTM
 def _aligned16(t: torch.Tensor) -> torch.Tensor:
     t = t.contiguous()
