@@ -6,13 +6,16 @@ SURVEY.md §2.12): ResidualRecurrentEncoder (emulated-bidirectional LSTM
 layer 0 + unidirectional residual LSTMs), ResidualRecurrentDecoder with
 Bahdanau RecurrentAttention and a Classifier head, hidden=1024,
 vocab=32320. LSTM layers are ops.modules.LSTM: torch.nn.LSTM (MIOpen RNN on
-ROCm) by default, the native step kernels with DDLB_LSTM=native; the emulated bidirectional layer uses the hand-written revert_varlen
-HIP kernel (ops/csrc/seq_utils.hip) with a torch fallback on CPU."""
+ROCm) by default, the native step kernels with DDLB_LSTM=native; the
+emulated bidirectional layer uses the hand-written revert_varlen HIP kernel
+(ops/csrc/seq_utils.hip) with a torch fallback on CPU. The attention's two
+backend choices (DDLB_ATTN_SCORE, DDLB_ATTN_CTX) and the LSTM's are rows of
+``ops.switches``, resolved on every forward; nothing here reads the
+environment itself."""
 
 from __future__ import annotations
 
 import math
-import os
 from typing import Optional
 
 import torch
@@ -22,6 +25,7 @@ import torch.nn.functional as F
 from ddlbench_amd import ops as _ops
 from ddlbench_amd.ops import functional as NF
 from ddlbench_amd.ops.modules import LSTM
+from ddlbench_amd.ops.switches import resolve
 
 PAD, BOS, EOS = 0, 1, 2
 
@@ -140,25 +144,17 @@ class BahdanauAttention(nn.Module):
         self.ctx_backend = ctx_backend
 
     def resolve_ctx_backend(self) -> str:
-        """As resolve_backend, for the softmax and context product."""
-        backend = self.ctx_backend
-        if backend == "auto":
-            backend = os.environ.get("DDLB_ATTN_CTX", "library")
-        if backend not in ("library", "native", "torch"):
-            raise ValueError("attention context backend must be library, "
-                             f"native or torch, got {backend!r}")
-        return backend
+        """As resolve_backend, for the softmax and context product (the
+        "attn_ctx" switch)."""
+        return resolve("attn_ctx", None if self.ctx_backend == "auto"
+                       else self.ctx_backend)
 
     def resolve_backend(self) -> str:
-        """The backend the next forward uses; the environment is read here,
-        per call, and only while the module's own setting is "auto"."""
-        backend = self.backend
-        if backend == "auto":
-            backend = os.environ.get("DDLB_ATTN_SCORE", "auto")
-        if backend not in ("auto", "native", "torch"):
-            raise ValueError("attention score backend must be auto, native "
-                             f"or torch, got {backend!r}")
-        return backend
+        """The backend the next forward uses: the "attn_score" switch,
+        resolved per call, deferring to the environment only while the
+        module's own setting is "auto"."""
+        return resolve("attn_score", None if self.backend == "auto"
+                       else self.backend)
 
     def score(self, q, k, mask: Optional[torch.Tensor] = None):
         # q: (B, Tq, H'), k: (B, Tk, H'); masked keys score -65504

@@ -13,6 +13,7 @@ for gfx950 only (``python setup.py build_ext --inplace`` or
 
 from __future__ import annotations
 
+from ddlbench_amd.ops.switches import check
 
 _ext = None
 _ext_err: Exception | None = None
@@ -50,6 +51,11 @@ def require_extension():
     return ext
 
 
+def check_backend(backend: str) -> str:
+    """``backend`` if it is a kernel backend, else ValueError."""
+    return check("kernel", backend, ("auto", "native", "torch"))
+
+
 def use_native(tensor_or_device, backend: str = "auto") -> bool:
     """Decide native-vs-torch dispatch for an op.
 
@@ -58,17 +64,15 @@ def use_native(tensor_or_device, backend: str = "auto") -> bool:
     auto    -> native iff the tensor lives on a HIP device. On a GPU a
                missing extension is a hard error (no silent eager
                fallback — the framework's GPU compute path is the HIP
-               kernels)."""
+               kernels).
+    Anything else is a ValueError."""
     import torch
+    check_backend(backend)
     if backend == "torch":
         return False
     dev = (tensor_or_device.device
            if isinstance(tensor_or_device, torch.Tensor) else tensor_or_device)
-    on_gpu = dev.type == "cuda"
-    if backend == "native":
-        require_extension()
-        return True
-    if on_gpu:
+    if backend == "native" or dev.type == "cuda":
         require_extension()
         return True
     return False

@@ -2,7 +2,7 @@
 
 Forward and data-grad run on the hand-written NHWC bf16 kernels
 (csrc/conv_mfma*.hip) and the weight-grad on the transpose-read kernel
-(csrc/conv_wgrad.hip) — the full conv triple is in-tree by default.
+(csrc/conv_wgrad.hip) — the full conv triple is in-tree.
 
 Eligibility: bf16, channels_last, groups=1, dilation=1, C%8==0, K%8==0.
 ``convert_convs(model)`` swaps every eligible nn.Conv2d for Conv2dMFMA.
@@ -15,28 +15,27 @@ the small-C kernels of csrc/conv_stem.hip (forward + weight-grad) through
 Grouped 3x3 convs (ResNeXt's conv2) likewise stay on the library by
 default; ``DDLB_GROUPED=native`` (or ``convert_convs(model,
 grouped="native")``) runs the forward, data-grad and weight-grad kernels of
-csrc/conv_grouped.hip through ``Conv2dGrouped``."""
+csrc/conv_grouped.hip through ``Conv2dGrouped``.
+
+Every DDLB_* switch here is a row of ``ops.switches``: DDLB_CONV_TAIL is
+resolved once at import (``NATIVE_TAIL``), DDLB_JOIN per forward, and
+DDLB_STEM, DDLB_GROUPED and DDLB_MAXPOOL per ``convert_convs`` call."""
 
 from __future__ import annotations
-
-import os
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from ddlbench_amd import ops as _ops
-
-# weight-grad backend: the native kernel (conv_wgrad.hip) by default —
-# DDLB_WGRAD=library opts back into aten's conv backward
-_WGRAD = os.environ.get("DDLB_WGRAD", "mfma")
+from ddlbench_amd.ops.switches import enabled, resolve
 
 # The backward's layout/dtype tail runs in native kernels: the dgrad
 # weight layout is one tiled transpose (conv_weight_dgrad_layout) and the
 # weight-grad kernels write the weight's dtype and layout themselves
 # (conv_igemm_wgrad_bf16). False restores the eager-tensor tail (a strided
 # permute copy, fp32 dw + cast) — same values, kept for comparison.
-NATIVE_TAIL = os.environ.get("DDLB_CONV_TAIL", "native") != "eager"
+NATIVE_TAIL = resolve("conv_tail") == "native"
 
 _CL = torch.channels_last
 
@@ -66,21 +65,15 @@ def _conv_backward(ctx, dy, add=None, gate=None):
                                   x.size(2), x.size(3), ctx.stride,
                                   ctx.pad, add, gate)
     if ctx.needs_input_grad[1]:
-        if _WGRAD == "mfma" and NATIVE_TAIL \
-                and weight.dtype == torch.bfloat16:
+        if NATIVE_TAIL and weight.dtype == torch.bfloat16:
             dw = ext.conv_igemm_wgrad_bf16(x, dy, weight.shape[2],
                                            weight.shape[3], ctx.stride,
                                            ctx.pad)
-        elif _WGRAD == "mfma":
+        else:
             dw = _dw_to_weight_layout(
                 ext.conv_igemm_wgrad(x, dy, weight.shape[2],
                                      weight.shape[3], ctx.stride,
                                      ctx.pad), weight)
-        else:
-            dw = torch.ops.aten.convolution_backward(
-                dy, x, weight, None, [ctx.stride, ctx.stride],
-                [ctx.pad, ctx.pad], [1, 1], False, [0, 0], 1,
-                [False, True, False])[1]
     return dx, dw
 
 
@@ -155,7 +148,7 @@ class _ConvMFMAJoin(torch.autograd.Function):
 
 def join_enabled() -> bool:
     """DDLB_JOIN=0 (read per call) restores the unfused residual join."""
-    return os.environ.get("DDLB_JOIN", "1") != "0"
+    return enabled("join")
 
 
 def mfma_eligible(conv: nn.Conv2d, x_dtype=torch.bfloat16) -> bool:
@@ -371,16 +364,6 @@ class Conv2dGrouped(_NativeConv2d):
                         1, self.groups)
 
 
-def _mode(value, env, what):
-    """A "native"/"library" switch; None reads the environment variable."""
-    if value is None:
-        value = os.environ.get(env, "library")
-    if value not in ("native", "library"):
-        raise ValueError(
-            f"{what} must be 'native' or 'library', got {value!r}")
-    return value
-
-
 def convert_convs(model: nn.Module, dtype=torch.bfloat16,
                   stem=None, grouped=None) -> int:
     """Replace eligible nn.Conv2d children with Conv2dMFMA and eligible
@@ -392,8 +375,8 @@ def convert_convs(model: nn.Module, dtype=torch.bfloat16,
     Conv2dStem and counts them. ``stem=None`` reads DDLB_STEM at call
     time. ``grouped`` does the same for grouped_eligible 3x3 convs
     (Conv2dGrouped, DDLB_GROUPED)."""
-    stem = _mode(stem, "DDLB_STEM", "stem")
-    grouped = _mode(grouped, "DDLB_GROUPED", "grouped")
+    stem = resolve("stem", stem)
+    grouped = resolve("grouped", grouped)
     count = 0
     for parent in model.modules():
         for name, child in list(parent.named_children()):
@@ -408,8 +391,7 @@ def convert_convs(model: nn.Module, dtype=torch.bfloat16,
             elif grouped == "native" and grouped_eligible(child, dtype):
                 setattr(parent, name, Conv2dGrouped(child))
                 count += 1
-    if dtype == torch.bfloat16 and \
-            os.environ.get("DDLB_MAXPOOL", "1") != "0":
+    if dtype == torch.bfloat16 and enabled("maxpool"):
         from ddlbench_amd.ops.pool import convert_maxpools
         count += convert_maxpools(model)
     return count

@@ -6,13 +6,13 @@ error there if the extension is missing), torch composition on CPU."""
 
 from __future__ import annotations
 
-import os
 from typing import Optional
 
 import torch
 import torch.nn.functional as F
 
 from ddlbench_amd import ops as _ops
+from ddlbench_amd.ops.switches import enabled
 
 _ACT = {"none": 0, "relu": 1, "relu6": 2}
 
@@ -41,7 +41,7 @@ def _apply_act(v: torch.Tensor, act: str) -> torch.Tensor:
 def gate_enabled() -> bool:
     """DDLB_GATE=0 (read per call) restores the materialised shortcut
     gradient at the residual joins."""
-    return os.environ.get("DDLB_GATE", "1") != "0"
+    return enabled("gate")
 
 
 class GateSlot:
@@ -394,9 +394,6 @@ def attention_context(scores: torch.Tensor, values: torch.Tensor,
     ``values`` may be strided in its first two dimensions (h stride 1): the
     native path reads it in place. Above ``ATTN_CTX_MAX_TK`` keys "auto"
     takes the torch composition and "native" raises."""
-    if backend not in ("auto", "native", "torch"):
-        raise ValueError("attention_context backend must be auto, native or "
-                         f"torch, got {backend!r}")
     native = _ops.use_native(scores, backend)
     if native:
         why = _attn_ctx_native_reject(scores, values)
@@ -435,6 +432,26 @@ def _aligned16(t: torch.Tensor) -> torch.Tensor:
     return t if t.data_ptr() % 16 == 0 else t.clone()
 
 
+def _lstm_fwd(x, w_ih, w_hh, b_ih, b_hh, h0, c0, save_gates: bool):
+    """The input projection (a library GEMM), the operands as the step
+    kernels want them (contiguous, 16-byte aligned, fp32 bias sum and cell
+    state) and the recurrence. Returns ``(y, cs, gates, prepared)`` where
+    ``prepared`` is the ``(x, w_hh, h0, c0f)`` the backward reads; without
+    ``save_gates`` the gates are not written."""
+    ext = _ops.require_extension()
+    T, B, I = x.shape
+    H = w_hh.size(1)
+    x = x.contiguous()
+    w_hh = _aligned16(w_hh)
+    xproj = torch.mm(x.view(T * B, I), w_ih.t()).view(T, B, 4 * H)
+    bias = b_ih.float() + b_hh.float()
+    h0 = _aligned16(h0) if h0 is not None else None
+    c0f = c0.float().contiguous() if c0 is not None else None
+    y, cs, gates = ext.lstm_fwd(_aligned16(xproj), w_hh, bias, h0, c0f,
+                                save_gates)
+    return y, cs, gates, (x, w_hh, h0, c0f)
+
+
 class _NativeLSTM(torch.autograd.Function):
     """Single-layer time-major bf16 LSTM. The two input-side GEMMs and the
     weight-gradient GEMMs are library calls outside the time loop; the
@@ -444,17 +461,8 @@ class _NativeLSTM(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, h0, c0):
-        ext = _ops.require_extension()
-        T, B, I = x.shape
-        H = w_hh.size(1)
-        x = x.contiguous()
-        w_hh = _aligned16(w_hh)
-        xproj = torch.mm(x.view(T * B, I), w_ih.t()).view(T, B, 4 * H)
-        bias = b_ih.float() + b_hh.float()
-        h0 = _aligned16(h0) if h0 is not None else None
-        c0f = c0.float().contiguous() if c0 is not None else None
-        y, cs, gates = ext.lstm_fwd(_aligned16(xproj), w_hh, bias, h0, c0f,
-                                    True)
+        y, cs, gates, (x, w_hh, h0, c0f) = _lstm_fwd(
+            x, w_ih, w_hh, b_ih, b_hh, h0, c0, True)
         ctx.save_for_backward(x, w_ih, w_hh, y, cs, gates, h0, c0f)
         ctx.set_materialize_grads(False)
         ctx.bias_dtypes = (b_ih.dtype, b_hh.dtype)
@@ -526,9 +534,6 @@ def lstm(x: torch.Tensor, w_ih: torch.Tensor, w_hh: torch.Tensor,
     in the HIP step kernels and raises NotImplementedError for anything it
     cannot run; ``backend="torch"`` is the plain time-loop composition in
     whatever dtype it is given."""
-    if backend not in ("auto", "native", "torch"):
-        raise ValueError("lstm backend must be auto, native or torch, got "
-                         f"{backend!r}")
     if x.dim() != 3:
         raise ValueError(f"lstm: x must be (T, B, I), got {tuple(x.shape)}")
     T, B, _ = x.shape
@@ -539,31 +544,20 @@ def lstm(x: torch.Tensor, w_ih: torch.Tensor, w_hh: torch.Tensor,
     if hx is not None:
         h0, c0 = hx
         h0, c0 = h0.reshape(B, H), c0.reshape(B, H)
-    native = backend == "native" or (backend == "auto"
-                                     and x.device.type == "cuda")
-    if native:
+    if _ops.use_native(x, backend):
         why = _lstm_native_reject(x, w_hh)
         if why is not None:
             raise NotImplementedError(
                 f"native LSTM does not support {why}; pass "
                 "backend=\"torch\" for the composition")
-        _ops.require_extension()
         tensors = (x, w_ih, w_hh, b_ih, b_hh, h0, c0)
         if torch.is_grad_enabled() and any(
                 t is not None and t.requires_grad for t in tensors):
             y, h_T, c_T = _NativeLSTM.apply(*tensors)
             return y, (h_T, c_T)
         # nothing to differentiate (greedy / beam decode): the gates are
-        # not even written
-        ext = _ops.require_extension()
-        x = x.detach().contiguous()
-        xproj = torch.mm(x.view(T * B, -1), w_ih.detach().t())
-        y, cs, _ = ext.lstm_fwd(
-            _aligned16(xproj.view(T, B, 4 * H)), _aligned16(w_hh.detach()),
-            b_ih.detach().float() + b_hh.detach().float(),
-            _aligned16(h0.detach()) if h0 is not None else None,
-            c0.detach().float().contiguous() if c0 is not None else None,
-            False)
+        # not even written, and autograd records nothing
+        y, cs, _, _ = _lstm_fwd(*tensors, False)
         return y, (y[-1:].clone(), cs[-1:].to(x.dtype))
     if h0 is None:
         h0 = x.new_zeros(B, H)

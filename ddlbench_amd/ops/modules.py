@@ -4,17 +4,18 @@
 model zoo with one fused op; ``DepthwiseConv3x3`` replaces
 Conv2d(groups=channels). Both keep plain-PyTorch semantics (state dict
 compatible with nn.BatchNorm2d / nn.Conv2d field names). ``LSTM`` is
-nn.LSTM with a choice of recurrence backend."""
+nn.LSTM with a choice of recurrence backend, the "lstm" row of
+``ops.switches`` (DDLB_LSTM)."""
 
 from __future__ import annotations
 
-import os
 from typing import Optional
 
 import torch
 import torch.nn as nn
 
-from ddlbench_amd.ops import functional as NF
+from ddlbench_amd.ops import check_backend, functional as NF
+from ddlbench_amd.ops.switches import resolve
 
 # module-level default backend — engines set this once from the config
 _DEFAULT_BACKEND = "auto"
@@ -22,8 +23,7 @@ _DEFAULT_BACKEND = "auto"
 
 def set_default_backend(backend: str) -> None:
     global _DEFAULT_BACKEND
-    assert backend in ("auto", "native", "torch")
-    _DEFAULT_BACKEND = backend
+    _DEFAULT_BACKEND = check_backend(backend)
 
 
 def default_backend() -> str:
@@ -123,14 +123,11 @@ class LSTM(nn.LSTM):
         self.backend = backend
 
     def resolve_backend(self) -> str:
-        """The backend the next forward uses; the environment is read here,
-        per call, and only while the module's own setting is "auto"."""
-        backend = self.backend
-        if backend == "auto":
-            backend = os.environ.get("DDLB_LSTM", "auto")
-        if backend not in ("auto", "native", "library"):
-            raise ValueError("LSTM backend must be auto, native or library, "
-                             f"got {backend!r}")
+        """The backend the next forward uses: the "lstm" switch, resolved
+        per call, deferring to the environment only while the module's own
+        setting is "auto"."""
+        backend = resolve("lstm",
+                          None if self.backend == "auto" else self.backend)
         return "library" if backend == "auto" else backend
 
     def _native_reject(self, x) -> Optional[str]:

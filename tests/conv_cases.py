@@ -17,6 +17,7 @@ plan functions (ext.conv_igemm_plan / ext.conv_wgrad_plan), and
 the dispatch that silently un-covers a path fails those assertions."""
 
 import collections
+import contextlib
 import functools
 import os
 
@@ -225,18 +226,26 @@ def exact_mismatches(got, ref64, dtype):
 
 
 # ------------------------------------------------------- plans -> coverage
+@contextlib.contextmanager
+def env(name, value):
+    """Environment variable ``name`` set to ``value`` inside the block,
+    restored (or unset again) after it."""
+    prev = os.environ.get(name)
+    os.environ[name] = value
+    try:
+        yield
+    finally:
+        if prev is None:
+            os.environ.pop(name, None)
+        else:
+            os.environ[name] = prev
+
+
 def igemm_plans(ext, shape, dgrad, v2):
     """ext.conv_igemm_plan under DDLB_CONV_V2 = v2 ("1" or "0")."""
     N, C, H, W, K, R, stride, pad = shape
-    old = os.environ.get("DDLB_CONV_V2")
-    os.environ["DDLB_CONV_V2"] = v2
-    try:
+    with env("DDLB_CONV_V2", v2):
         return ext.conv_igemm_plan(N, C, H, W, K, R, R, stride, pad, dgrad)
-    finally:
-        if old is None:
-            del os.environ["DDLB_CONV_V2"]
-        else:
-            os.environ["DDLB_CONV_V2"] = old
 
 
 def wgrad_plan(ext, shape):

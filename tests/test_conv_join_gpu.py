@@ -6,12 +6,12 @@ the one bf16 add the eager kernel does), for both kernel structures and
 for the stride-2 paths; blocks wired through ``forward_join`` must compute
 what the unfused blocks compute. All @gpu."""
 
-import contextlib
 import copy
-import os
 
 import pytest
 import torch
+
+from conv_cases import env as _env
 
 pytestmark = pytest.mark.gpu
 
@@ -27,19 +27,6 @@ def _require_ext():
     from ddlbench_amd import ops
     assert ops.extension_available(), \
         "native extension must be present on the GPU box"
-
-
-@contextlib.contextmanager
-def _env(name, value):
-    prev = os.environ.get(name)
-    os.environ[name] = value
-    try:
-        yield
-    finally:
-        if prev is None:
-            os.environ.pop(name, None)
-        else:
-            os.environ[name] = prev
 
 
 # (N, C, H, W, K, R, stride, pad): dgrad GEMM is M=N*H*W, Nd=C, Kd=R*R*K

@@ -8,13 +8,12 @@ compute the same gradients with DDLB_GATE=1 and DDLB_GATE=0 — all bit for
 bit (compared on the raw 16/32-bit patterns, so zero signs count). A
 shortcut gradient that was tampered with must raise. All @gpu."""
 
-import contextlib
 import copy
-import os
 
 import pytest
 import torch
 
+from conv_cases import env as _env
 from test_conv_join_gpu import _SHAPES
 
 pytestmark = pytest.mark.gpu
@@ -31,19 +30,6 @@ def _require_ext():
     from ddlbench_amd import ops
     assert ops.extension_available(), \
         "native extension must be present on the GPU box"
-
-
-@contextlib.contextmanager
-def _env(name, value):
-    prev = os.environ.get(name)
-    os.environ[name] = value
-    try:
-        yield
-    finally:
-        if prev is None:
-            os.environ.pop(name, None)
-        else:
-            os.environ[name] = prev
 
 
 def _bits_nchw(mask, like):

@@ -417,7 +417,7 @@ def test_model_trains_on_native_kernels():
 def test_conv_v2_matches_v1(shape):
     """The deep-pipeline (v2) and 128-tile (v1) structures accumulate
     the identical K-ordered f32 MFMA chain -> bitwise-equal outputs."""
-    import os
+    from conv_cases import env
     from ddlbench_amd.ops import require_extension
     ext = require_extension()
     N, C, H, W, K, R, stride, pad = shape
@@ -432,19 +432,12 @@ def test_conv_v2_matches_v1(shape):
     dy = torch.randn(N, K, OH, OH, device=dev,
                      dtype=torch.bfloat16).contiguous(memory_format=cl)
     w_perm = w.permute(1, 2, 3, 0).contiguous()
-    prev = os.environ.get("DDLB_CONV_V2")
-    try:
-        os.environ["DDLB_CONV_V2"] = "1"
+    with env("DDLB_CONV_V2", "1"):
         y2 = ext.conv_igemm_fwd(x, w, stride, pad)
         dx2 = ext.conv_igemm_dgrad(dy, w_perm, N, C, H, W, stride, pad)
-        os.environ["DDLB_CONV_V2"] = "0"
+    with env("DDLB_CONV_V2", "0"):
         y1 = ext.conv_igemm_fwd(x, w, stride, pad)
         dx1 = ext.conv_igemm_dgrad(dy, w_perm, N, C, H, W, stride, pad)
-    finally:
-        if prev is None:
-            os.environ.pop("DDLB_CONV_V2", None)
-        else:
-            os.environ["DDLB_CONV_V2"] = prev
     assert torch.equal(y1, y2), "fwd structures disagree"
     assert torch.equal(dx1, dx2), "dgrad structures disagree"
 
