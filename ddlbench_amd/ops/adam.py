@@ -10,7 +10,8 @@ import torch
 from torch.optim import Optimizer
 
 from ddlbench_amd import ops as _ops
-from ddlbench_amd.ops.sgd import _same_dense_layout
+from ddlbench_amd.ops.sgd import (_cache_stale, _grad_ptr_table,
+                                  _layout_matched_grads)
 
 
 class FusedAdam(Optimizer):
@@ -89,34 +90,29 @@ class FusedAdam(Optimizer):
             t = self.state[ps[0]]["step"]
             key = (gi, dtype)
             cached = self._cache.get(key)
-            if cached is None or len(cached["params"]) != len(ps):
-                prefix = torch.zeros(len(ps), dtype=torch.int64)
+            n = len(ps)
+            ptrs = ([p.data_ptr() for p in ps]
+                    + [self.state[p]["exp_avg"].data_ptr() for p in ps]
+                    + [self.state[p]["exp_avg_sq"].data_ptr() for p in ps])
+            if _cache_stale(cached, ps, ptrs):
+                prefix = torch.zeros(n, dtype=torch.int64)
                 total = 0
                 for i, p in enumerate(ps):
                     prefix[i] = total
                     total += p.numel()
                 cached = {
-                    "params": ps, "total": total, "prefix": prefix.to(dev),
+                    "params": ps, "ptrs_host": ptrs, "total": total,
+                    "prefix": prefix.to(dev),
                     "ptr_params": torch.tensor(
-                        [p.data_ptr() for p in ps],
-                        dtype=torch.int64).to(dev),
+                        ptrs[:n], dtype=torch.int64).to(dev),
                     "ptr_ms": torch.tensor(
-                        [self.state[p]["exp_avg"].data_ptr() for p in ps],
-                        dtype=torch.int64).to(dev),
+                        ptrs[n:2 * n], dtype=torch.int64).to(dev),
                     "ptr_vs": torch.tensor(
-                        [self.state[p]["exp_avg_sq"].data_ptr()
-                         for p in ps], dtype=torch.int64).to(dev),
+                        ptrs[2 * n:], dtype=torch.int64).to(dev),
                 }
                 self._cache[key] = cached
-            for p in ps:
-                if not _same_dense_layout(p, p.grad):
-                    p.grad = p.grad.contiguous() if p.is_contiguous() \
-                        else p.grad.contiguous(
-                            memory_format=torch.channels_last)
-                assert _same_dense_layout(p, p.grad)
-            ptr_grads = torch.tensor([p.grad.data_ptr() for p in ps],
-                                     dtype=torch.int64).to(
-                                         dev, non_blocking=True)
+            grads = _layout_matched_grads(ps, "FusedAdam")
+            ptr_grads = _grad_ptr_table(cached, grads, dev)
             ext.fused_adam(cached["ptr_params"], ptr_grads,
                            cached["ptr_ms"], cached["ptr_vs"],
                            cached["prefix"], cached["total"], lr, b1, b2,

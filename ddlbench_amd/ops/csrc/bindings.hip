@@ -356,7 +356,8 @@ std::vector<torch::Tensor> ce_fwd(torch::Tensor logits,
   const int64_t B = logits.size(0), K = logits.size(1);
   auto s = cur_stream();
   auto fopt = logits.options().dtype(at::kFloat);
-  torch::Tensor lse = torch::empty({B}, fopt);
+  // row maximum and log-sum-exp above it, one row each (see ce_bwd_kernel)
+  torch::Tensor lse = torch::empty({2, B}, fopt);
   torch::Tensor loss_sum = torch::zeros({1}, fopt);
   dispatch_f32_bf16(logits, [&](auto tag) {
     using T = decltype(tag);
@@ -369,6 +370,9 @@ std::vector<torch::Tensor> ce_fwd(torch::Tensor logits,
 torch::Tensor ce_bwd(torch::Tensor logits, torch::Tensor target,
                      torch::Tensor lse, torch::Tensor gscale) {
   const int64_t B = logits.size(0), K = logits.size(1);
+  TORCH_CHECK(lse.dim() == 2 && lse.size(0) == 2 && lse.size(1) == B &&
+                  lse.is_contiguous(),
+              "ce_bwd: lse must be the (2, B) tensor ce_fwd returned");
   auto s = cur_stream();
   torch::Tensor dx = torch::empty_like(logits);
   dispatch_f32_bf16(logits, [&](auto tag) {

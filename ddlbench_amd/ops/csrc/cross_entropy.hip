@@ -47,9 +47,10 @@ __global__ void ce_fwd_wave_kernel(const T* __restrict__ logits,
   for (int64_t k = lane; k < K; k += WAVE) s += __expf(to_f32(row[k]) - m);
   s = wave_reduce_sum(s);
   if (lane == 0) {
-    const float l = m + __logf(s);
-    lse[b] = l;
-    atomicAdd(loss_sum, l - to_f32(row[target[b]]));
+    const float ls = __logf(s);
+    lse[b] = m;
+    lse[B + b] = ls;
+    atomicAdd(loss_sum, (m - to_f32(row[target[b]])) + ls);
   }
 }
 
@@ -98,12 +99,16 @@ __global__ void ce_fwd_block_kernel(const T* __restrict__ logits,
   auto sumop = [](float v) { return wave_reduce_sum(v); };
   s = block_reduce(s, tmp, sumop, 0.f);
   if (tid == 0) {
-    const float l = m + __logf(s);
-    lse[b] = l;
-    atomicAdd(loss_sum, l - to_f32(row[target[b]]));
+    const float ls = __logf(s);
+    lse[b] = m;
+    lse[B + b] = ls;
+    atomicAdd(loss_sum, (m - to_f32(row[target[b]])) + ls);
   }
 }
 
+// lse holds the row maximum m in lse[0..B) and log sum exp(x - m) in
+// lse[B..2B), kept apart: their fp32 sum would round at ulp(|m|), which for
+// large logits is far coarser than the loss and the probabilities.
 // dx = (softmax - onehot) * gscale   (gscale = dloss / B for mean)
 template <typename T>
 __global__ void ce_bwd_kernel(const T* __restrict__ logits,
@@ -116,7 +121,7 @@ __global__ void ce_bwd_kernel(const T* __restrict__ logits,
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
        i += stride) {
     const int64_t b = i / K, k = i - b * K;
-    float p = __expf(to_f32(logits[i]) - lse[b]);
+    float p = __expf((to_f32(logits[i]) - lse[b]) - lse[B + b]);
     if (k == target[b]) p -= 1.f;
     dx[i] = from_f32<T>(p * gscale[0]);
   }

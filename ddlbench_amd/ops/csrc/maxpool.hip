@@ -49,12 +49,15 @@ __global__ void maxpool_fwd_nhwc_kernel(
     const int oh = rem / OW, ow = rem - (rem / OW) * OW;
     float best[8];
     int barg[8];
+    const int ih0 = oh * stride - pad, iw0 = ow * stride - pad;
+    // start on the window's first in-bounds slot, not on slot 0 (which may
+    // be padding): an all -inf window then still names a real pixel
+    const int first = max(-ih0, 0) * k + max(-iw0, 0);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      best[j] = -3.4e38f;
-      barg[j] = 0;
+      best[j] = -INFINITY;
+      barg[j] = first;
     }
-    const int ih0 = oh * stride - pad, iw0 = ow * stride - pad;
     for (int kr = 0; kr < k; ++kr) {
       const int ih = ih0 + kr;
       if (ih < 0 || ih >= H) continue;
@@ -66,7 +69,8 @@ __global__ void maxpool_fwd_nhwc_kernel(
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const float f = b2f(v[j]);
-          if (f > best[j]) {
+          // first maximum wins a tie; the first NaN wins and stays
+          if (f > best[j] || (f != f && best[j] == best[j])) {
             best[j] = f;
             barg[j] = kr * k + ks;
           }

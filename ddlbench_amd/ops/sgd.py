@@ -24,6 +24,48 @@ def _same_dense_layout(p, g):
                for sz, ps, gs in zip(p.shape, p.stride(), g.stride()))
 
 
+def _cache_stale(cached, ps, ptrs):
+    """True when the cached device pointer tables no longer describe
+    ``ps``: another member (a same-length set with different members —
+    freeze/unfreeze, grads becoming None — would otherwise reuse stale
+    device pointers), or a member or state tensor whose storage moved
+    (``p.data = ...``, ``model.to(memory_format=...)`` after the first
+    step, a loaded state dict). ``ptrs`` is the host list of the
+    data_ptrs the tables would hold."""
+    return (cached is None or len(cached["params"]) != len(ps)
+            or any(a is not b for a, b in zip(cached["params"], ps))
+            or cached["ptrs_host"] != ptrs)
+
+
+def _layout_matched_grads(ps, who):
+    """The grads the fused kernel reads. It walks param/grad as flat
+    buffers in storage order — any dense layout works (NCHW or
+    channels_last) as long as grad strides match param's. On mismatch, hand
+    the kernel a layout-matched COPY without rebinding p.grad: a rebind
+    would orphan persistent DP bucket views (grads would silently stop
+    reaching the all-reduce payload)."""
+    grads = []
+    for p in ps:
+        g = p.grad
+        if not _same_dense_layout(p, g):
+            g = (g.contiguous() if p.is_contiguous()
+                 else g.contiguous(memory_format=torch.channels_last))
+            assert _same_dense_layout(p, g), \
+                f"{who} needs grads with the param's layout"
+        grads.append(g)
+    return grads
+
+
+def _grad_ptr_table(cached, grads, dev):
+    """Device array of the grads' pointers. Grads in persistent buckets
+    (DP) keep their pointers — re-upload only when one moved."""
+    gptrs = [g.data_ptr() for g in grads]
+    if cached.get("grad_ptrs_host") != gptrs:
+        cached["ptr_grads"] = torch.tensor(gptrs, dtype=torch.int64).to(
+            dev, non_blocking=True)
+        cached["grad_ptrs_host"] = gptrs
+    return cached["ptr_grads"]
+
 
 class FusedSGD(Optimizer):
     def __init__(self, params, lr: float, momentum: float = 0.0,
@@ -82,66 +124,39 @@ class FusedSGD(Optimizer):
             dev = ps[0].device
             key = (gi, dtype)
             cached = self._cache.get(key)
-            first_step = False
-            # invalidate on any identity change, not just count: a same-
-            # length set with different members (freeze/unfreeze, grads
-            # becoming None) would otherwise reuse stale device pointers
-            if (cached is None or len(cached["params"]) != len(ps)
-                    or any(a is not b
-                           for a, b in zip(cached["params"], ps))):
-                numels = [p.numel() for p in ps]
+            # momentum buffers are zero-filled when created, so a new one
+            # needs no first-step kernel variant of its own (mu * 0 + d is
+            # d); the m = d variant runs when every buffer is new
+            fresh = 0
+            for p in ps:
+                st = self.state[p]
+                if mu and "momentum_buffer" not in st:
+                    st["momentum_buffer"] = torch.zeros(
+                        p.shape, dtype=torch.float32, device=dev)
+                    fresh += 1
+            first_step = fresh == len(ps)
+            moms = [self.state[p]["momentum_buffer"].data_ptr() if mu else 0
+                    for p in ps]
+            ptrs = [p.data_ptr() for p in ps] + moms
+            if _cache_stale(cached, ps, ptrs):
                 prefix = torch.zeros(len(ps), dtype=torch.int64)
                 total = 0
-                for i, n in enumerate(numels):
+                for i, p in enumerate(ps):
                     prefix[i] = total
-                    total += n
-                moms = []
-                for p in ps:
-                    st = self.state[p]
-                    if mu and "momentum_buffer" not in st:
-                        st["momentum_buffer"] = torch.zeros(
-                            p.shape, dtype=torch.float32, device=dev)
-                        first_step = True
-                    moms.append(st["momentum_buffer"].data_ptr() if mu else 0)
+                    total += p.numel()
                 cached = {
                     "params": ps,
+                    "ptrs_host": ptrs,
                     "total": total,
                     "prefix": prefix.to(dev),
                     "ptr_params": torch.tensor(
-                        [p.data_ptr() for p in ps], dtype=torch.int64).to(dev),
+                        ptrs[:len(ps)], dtype=torch.int64).to(dev),
                     "ptr_moms": torch.tensor(
                         moms, dtype=torch.int64).to(dev),
                 }
                 self._cache[key] = cached
-                cached["first_step"] = first_step
-            first_step = cached.pop("first_step", False)
-            # the fused kernel walks param/grad as flat buffers in
-            # storage order — any dense layout works (NCHW or
-            # channels_last) as long as grad strides match param's.
-            # On mismatch, hand the kernel a layout-matched COPY without
-            # rebinding p.grad: a rebind would orphan persistent DP
-            # bucket views (grads would silently stop reaching the
-            # all-reduce payload).
-            grads = []
-            for p in ps:
-                g = p.grad
-                if not _same_dense_layout(p, g):
-                    g = (g.contiguous() if p.is_contiguous()
-                         else g.contiguous(
-                             memory_format=torch.channels_last))
-                    assert _same_dense_layout(p, g), \
-                        "FusedSGD needs grads with the param's layout"
-                grads.append(g)
-            # grads in persistent buckets (DP) keep their pointers —
-            # re-upload the pointer array only when one moved
-            gptrs = [g.data_ptr() for g in grads]
-            if cached.get("grad_ptrs_host") == gptrs:
-                ptr_grads = cached["ptr_grads"]
-            else:
-                ptr_grads = torch.tensor(gptrs, dtype=torch.int64).to(
-                    dev, non_blocking=True)
-                cached["grad_ptrs_host"] = gptrs
-                cached["ptr_grads"] = ptr_grads
+            grads = _layout_matched_grads(ps, "FusedSGD")
+            ptr_grads = _grad_ptr_table(cached, grads, dev)
             ext.fused_sgd(cached["ptr_params"], ptr_grads,
                           cached["ptr_moms"], cached["prefix"],
                           cached["total"], lr, mu, wd, first_step,
