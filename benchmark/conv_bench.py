@@ -19,7 +19,11 @@ only those (plus the plain data-grad) per shape.
 
 ``--grouped`` times the seven distinct grouped 3x3 convs of
 resnext50_32x4d (native csrc/conv_grouped.hip vs the library) in all three
-directions, with each direction's share of its byte floor."""
+directions, with each direction's share of its byte floor.
+
+``--depthwise`` times NASNet-A mobile's 5x5 / 7x7 depthwise convs at
+ImageNet and CIFAR geometry (native csrc/conv_depthwise.hip vs the library)
+the same way."""
 
 import argparse
 import json
@@ -197,6 +201,91 @@ def bench_grouped(args):
         print(json.dumps(res), flush=True)
 
 
+# measured streaming rate of the MI355X (TB/s): the byte floor of the
+# depthwise rows
+STREAM_TBS = 6.29
+
+def nasnet_depthwise_shapes():
+    """(dataset, C, H/W, K, stride) of every distinct 5x5 / 7x7 depthwise
+    conv nasnetamobile runs at ImageNet and CIFAR geometry, read off one
+    CPU forward of the model itself."""
+    import torch.nn as nn
+    from ddlbench_amd.config import DATASET_SHAPES
+    from ddlbench_amd.models import build_model
+    out = []
+    for dataset in ("imagenet", "cifar10"):
+        model = build_model(dataset, "nasnetamobile").eval()
+
+        def hook(mod, inp, _out):
+            key = (dataset, mod.in_channels, inp[0].shape[2],
+                   mod.kernel_size[0], mod.stride[0])
+            if key not in out:
+                out.append(key)
+
+        for mod in model.modules():
+            if isinstance(mod, nn.Conv2d) and mod.groups == mod.in_channels \
+                    and mod.kernel_size[0] in (5, 7):
+                mod.register_forward_hook(hook)
+        C, H, W = DATASET_SHAPES[dataset][:3]
+        with torch.no_grad():
+            model(torch.zeros(1, C, H, W))
+    return out
+
+
+def bench_depthwise(args):
+    """Native csrc/conv_depthwise.hip against the library, all three
+    directions, alternating in one process; per direction the share of the
+    byte floor (every operand read or written once at the measured
+    streaming rate) the native time is."""
+    from ddlbench_amd.ops import require_extension
+    ext = require_extension()
+    dev = torch.device("cuda", 0)
+    cl = torch.channels_last
+    N = args.batch
+    for dataset, C, HW, K, stride in nasnet_depthwise_shapes():
+        pad = K // 2
+        OHW = (HW + 2 * pad - K) // stride + 1
+        x = torch.randn(N, C, HW, HW, device=dev,
+                        dtype=torch.bfloat16).contiguous(memory_format=cl)
+        w = torch.randn(C, 1, K, K, device=dev, dtype=torch.bfloat16)
+        dy = torch.randn(N, C, OHW, OHW, device=dev,
+                         dtype=torch.bfloat16).contiguous(memory_format=cl)
+
+        def library_bwd(mask):
+            return torch.ops.aten.convolution_backward(
+                dy, x, w, None, [stride, stride], [pad, pad], [1, 1], False,
+                [0, 0], C, mask)
+
+        fns = {
+            "native_fwd": lambda: ext.conv_depthwise_fwd(x, w, stride),
+            "library_fwd": lambda: torch.nn.functional.conv2d(
+                x, w, None, stride, pad, 1, C),
+            "native_dgrad": lambda: ext.conv_depthwise_dgrad(
+                dy, w, N, C, HW, HW, stride),
+            "library_dgrad": lambda: library_bwd([True, False, False]),
+            "native_wgrad": lambda: ext.conv_depthwise_wgrad(
+                x, dy, K, stride),
+            "library_wgrad": lambda: library_bwd([False, True, False]),
+        }
+        res = {"dataset": dataset, "shape": f"C{C}_HW{HW}_K{K}_s{stride}",
+               "batch": N}
+        # native and library alternate; two passes, the lower time counts
+        best = {}
+        for _ in range(2):
+            for name, fn in fns.items():
+                t = bench_op(fn, args.iters, args.warmup)
+                best[name] = min(best.get(name, t), t)
+        for name, t in best.items():
+            res[name + "_ms"] = round(t * 1e3, 4)
+        floor = 2 * (x.numel() + w.numel() + dy.numel()) / (STREAM_TBS * 1e12)
+        res["floor_ms"] = round(floor * 1e3, 4)
+        for d in ("fwd", "dgrad", "wgrad"):
+            res[d + "_floor_share"] = round(floor / best["native_" + d], 3)
+            res[d + "_native_over_library"] = round(
+                best["native_" + d] / best["library_" + d], 3)
+        print(json.dumps(res), flush=True)
+
+
 def join_columns(ext, dy, w_perm, x, stride, pad, args):
     """dgrad+add: fused epilogue addend vs dgrad followed by a torch add
     (deep-pipeline structure; g stands in for the shortcut's gradient)."""
@@ -234,6 +323,9 @@ def main():
     p.add_argument("--grouped", action="store_true",
                    help="time the grouped 3x3 convs of resnext50_32x4d "
                         "(native vs library, fwd/dgrad/wgrad) instead")
+    p.add_argument("--depthwise", action="store_true",
+                   help="time the 5x5/7x7 depthwise convs of nasnetamobile "
+                        "(native vs library, fwd/dgrad/wgrad) instead")
     p.add_argument("--join", action="store_true",
                    help="per shape, only the data-grad and the dgrad+add "
                         "columns (fused addend vs dgrad then torch add)")
@@ -245,6 +337,9 @@ def main():
         return
     if args.grouped:
         bench_grouped(args)
+        return
+    if args.depthwise:
+        bench_depthwise(args)
         return
     from ddlbench_amd.ops.conv import conv2d_mfma
     dev = torch.device("cuda", 0)

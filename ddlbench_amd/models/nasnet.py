@@ -8,7 +8,9 @@ Normal cells with Reduction cells between stacks; every cell combines
 its two predecessor feature maps through five op-pairs (separable convs
 3x3/5x5/7x7 as depthwise+pointwise twice, avg/max pools, identity) and
 concatenates the block outputs. Separable 3x3 depthwise runs on the
-in-tree HIP kernel; 5x5/7x7 depthwise use the library grouped conv.
+in-tree HIP kernel; 5x5/7x7 depthwise use the library grouped conv
+unless ``convert_convs(model, depthwise="native")`` swaps them for the
+in-tree kernels of csrc/conv_depthwise.hip (opt-in).
 Cell wiring follows the paper's figure; the vendored copy's exact
 channel bookkeeping may differ in minor details (documented, not
 bit-claimed)."""

@@ -17,6 +17,12 @@ default; ``DDLB_GROUPED=native`` (or ``convert_convs(model,
 grouped="native")``) runs the forward, data-grad and weight-grad kernels of
 csrc/conv_grouped.hip through ``Conv2dGrouped``.
 
+Depthwise KxK convs (NASNet's 5x5 / 7x7 separable convs) stay on the
+library too; ``convert_convs(model, depthwise="native")`` runs the forward,
+data-grad and weight-grad kernels of csrc/conv_depthwise.hip through
+``Conv2dDepthwise``. That choice is an argument only: no environment
+variable selects it.
+
 Every DDLB_* switch here is a row of ``ops.switches``: DDLB_CONV_TAIL is
 resolved once at import (``NATIVE_TAIL``), DDLB_JOIN per forward, and
 DDLB_STEM, DDLB_GROUPED and DDLB_MAXPOOL per ``convert_convs`` call."""
@@ -28,7 +34,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ddlbench_amd import ops as _ops
-from ddlbench_amd.ops.switches import enabled, resolve
+from ddlbench_amd.ops.switches import check, enabled, resolve
 
 # The backward's layout/dtype tail runs in native kernels: the dgrad
 # weight layout is one tiled transpose (conv_weight_dgrad_layout) and the
@@ -364,8 +370,80 @@ class Conv2dGrouped(_NativeConv2d):
                         1, self.groups)
 
 
+class _ConvDepthwise(torch.autograd.Function):
+    """Depthwise KxK conv (pad K/2) on the kernels of
+    csrc/conv_depthwise.hip: forward, data-grad and weight-grad (bf16, the
+    weight's (C,1,K,K) memory), each backward direction only when its
+    gradient is needed."""
+
+    @staticmethod
+    def forward(ctx, x, weight, stride):
+        ext = _ops.require_extension()
+        x = x.contiguous(memory_format=_CL)
+        y = ext.conv_depthwise_fwd(x, weight.contiguous(), stride)
+        ctx.save_for_backward(x, weight)
+        ctx.stride = stride
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        ext = _ops.require_extension()
+        x, weight = ctx.saved_tensors
+        dy = dy.contiguous(memory_format=_CL)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = ext.conv_depthwise_dgrad(dy, weight.contiguous(), x.size(0),
+                                          x.size(1), x.size(2), x.size(3),
+                                          ctx.stride)
+        if ctx.needs_input_grad[1]:
+            # (C,1,K,K): dense memory is the same in every layout, so the
+            # weight's own strides describe the kernel's output
+            dw = ext.conv_depthwise_wgrad(x, dy, weight.shape[2], ctx.stride) \
+                .as_strided(weight.shape, weight.stride())
+        return dx, dw, None
+
+
+def conv2d_depthwise(x, weight, stride=1):
+    return _ConvDepthwise.apply(x, weight, stride)
+
+
+def depthwise_eligible(conv: nn.Conv2d, x_dtype=torch.bfloat16) -> bool:
+    """True for the problems csrc/conv_depthwise.hip supports: groups == C
+    in == C out, C % 4 == 0, square 3/5/7 kernel, pad K/2, stride 1 or 2,
+    dilation 1, no bias."""
+    k = conv.kernel_size[0]
+    return (x_dtype == torch.bfloat16
+            and conv.groups == conv.in_channels == conv.out_channels
+            and conv.in_channels % 4 == 0
+            and conv.dilation == (1, 1)
+            and conv.bias is None
+            and conv.kernel_size in ((3, 3), (5, 5), (7, 7))
+            and conv.stride in ((1, 1), (2, 2))
+            and conv.padding == (k // 2, k // 2))
+
+
+class Conv2dDepthwise(_NativeConv2d):
+    """Drop-in for a depthwise_eligible nn.Conv2d, running the depthwise
+    kernels."""
+
+    tag = "depthwise"
+
+    def __init__(self, conv: nn.Conv2d):
+        super().__init__(conv)
+        self.groups = conv.groups
+
+    def native(self, x):
+        return conv2d_depthwise(x, self.weight, self.stride)
+
+    def forward(self, x):
+        if x.is_cuda and x.dtype == torch.bfloat16:
+            return self.native(x)
+        return F.conv2d(x, self.weight, None, self.stride, self.padding,
+                        1, self.groups)
+
+
 def convert_convs(model: nn.Module, dtype=torch.bfloat16,
-                  stem=None, grouped=None) -> int:
+                  stem=None, grouped=None, depthwise="library") -> int:
     """Replace eligible nn.Conv2d children with Conv2dMFMA and eligible
     nn.MaxPool2d with the native NHWC pool. Returns the number of
     conversions.
@@ -374,9 +452,12 @@ def convert_convs(model: nn.Module, dtype=torch.bfloat16,
     leaves them as nn.Conv2d, "native" swaps stem_eligible ones for
     Conv2dStem and counts them. ``stem=None`` reads DDLB_STEM at call
     time. ``grouped`` does the same for grouped_eligible 3x3 convs
-    (Conv2dGrouped, DDLB_GROUPED)."""
+    (Conv2dGrouped, DDLB_GROUPED). ``depthwise="native"`` swaps
+    depthwise_eligible convs for Conv2dDepthwise; it has no environment
+    variable and defaults to "library"."""
     stem = resolve("stem", stem)
     grouped = resolve("grouped", grouped)
+    check("depthwise", depthwise, ("native", "library"))
     count = 0
     for parent in model.modules():
         for name, child in list(parent.named_children()):
@@ -390,6 +471,9 @@ def convert_convs(model: nn.Module, dtype=torch.bfloat16,
                 count += 1
             elif grouped == "native" and grouped_eligible(child, dtype):
                 setattr(parent, name, Conv2dGrouped(child))
+                count += 1
+            elif depthwise == "native" and depthwise_eligible(child, dtype):
+                setattr(parent, name, Conv2dDepthwise(child))
                 count += 1
     if dtype == torch.bfloat16 and enabled("maxpool"):
         from ddlbench_amd.ops.pool import convert_maxpools

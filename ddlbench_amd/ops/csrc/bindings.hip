@@ -1179,6 +1179,124 @@ torch::Tensor conv_grouped_wgrad(torch::Tensor x, torch::Tensor dy,
   return dw;
 }
 
+// ---- depthwise KxK conv (NHWC bf16) -----------------------------------
+// Supported problem of csrc/conv_depthwise.hip; a violation raises before
+// any launch. `act` is the x- or dy-like operand, already checked bf16
+// channels_last.
+static void check_depthwise_shape(const torch::Tensor& act, int64_t C,
+                                  int64_t K, int64_t stride) {
+  TORCH_CHECK(K == 3 || K == 5 || K == 7,
+              "conv_depthwise needs a square 3x3, 5x5 or 7x7 kernel");
+  TORCH_CHECK(stride == 1 || stride == 2,
+              "conv_depthwise needs stride 1 or 2");
+  TORCH_CHECK(C >= 4 && C % 4 == 0, "conv_depthwise needs C % 4 == 0");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(act.data_ptr()) %
+                      (C % 8 == 0 ? 16 : 8) == 0,
+              "conv_depthwise: tensors must be 16-byte aligned");
+}
+
+static int64_t check_depthwise_weight(const torch::Tensor& w,
+                                      const torch::Tensor& like, int64_t C) {
+  TORCH_CHECK(w.is_cuda() && w.scalar_type() == at::kBFloat16 &&
+                  w.device() == like.device(),
+              "conv_depthwise: w must be bf16 on the input's device");
+  TORCH_CHECK(w.dim() == 4 && w.size(0) == C && w.size(1) == 1 &&
+                  w.size(2) == w.size(3),
+              "conv_depthwise: w must be (C, 1, K, K)");
+  TORCH_CHECK(w.is_contiguous(), "conv_depthwise: w must be contiguous");
+  return w.size(2);
+}
+
+// x: (N,C,H,W) channels_last; w: the (C,1,K,K) weight; pad is K/2.
+// Returns channels_last y.
+torch::Tensor conv_depthwise_fwd(torch::Tensor x, torch::Tensor w,
+                                 int64_t stride) {
+  TORCH_CHECK(x.dim() == 4, "conv_depthwise: 4-D tensors only");
+  check_conv_operand(x, "x", "conv_depthwise");
+  const int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  const int64_t K = check_depthwise_weight(w, x, C);
+  check_depthwise_shape(x, C, K, stride);
+  check_conv_geometry("conv_depthwise", N, H, W, K, K, stride, K / 2);
+  const DwkPlan pl = dwk_plan(N, C, H, W, (int)K, (int)stride);
+  auto y = empty_nhwc(x, N, C, pl.OH, pl.OW);
+  launch_conv_depthwise_fwd(pl, x.data_ptr(), w.data_ptr(), y.data_ptr(), N,
+                            C, H, W, (int)K, (int)stride, cur_stream());
+  return y;
+}
+
+// dy: (N,C,OH,OW) channels_last; w as in the forward (the kernels read it
+// reversed or by parity themselves). Returns channels_last dx (N,C,H,W),
+// fully written.
+torch::Tensor conv_depthwise_dgrad(torch::Tensor dy, torch::Tensor w,
+                                   int64_t N, int64_t C, int64_t H,
+                                   int64_t W, int64_t stride) {
+  TORCH_CHECK(dy.dim() == 4, "conv_depthwise: 4-D tensors only");
+  check_conv_operand(dy, "dy", "conv_depthwise");
+  TORCH_CHECK(dy.size(1) == C, "conv_depthwise: dy channels do not match C");
+  const int64_t K = check_depthwise_weight(w, dy, C);
+  check_depthwise_shape(dy, C, K, stride);
+  check_conv_geometry("conv_depthwise", N, H, W, K, K, stride, K / 2);
+  check_conv_dy("conv_depthwise", dy, N, H, W, K, K, stride, K / 2);
+  const DwkPlan pl = dwk_plan((int)N, (int)C, (int)H, (int)W, (int)K,
+                              (int)stride);
+  auto dx = empty_nhwc(dy, N, C, H, W);
+  launch_conv_depthwise_dgrad(pl, dy.data_ptr(), w.data_ptr(), dx.data_ptr(),
+                              (int)N, (int)C, (int)H, (int)W, (int)K,
+                              (int)stride, cur_stream());
+  return dx;
+}
+
+// x: (N,C,H,W) channels_last; dy: (N,C,OH,OW) channels_last. Returns the
+// bf16 (C,1,K,K) dw, each element the round-to-nearest-even bf16 of its
+// fp32 sum.
+torch::Tensor conv_depthwise_wgrad(torch::Tensor x, torch::Tensor dy,
+                                   int64_t K, int64_t stride) {
+  TORCH_CHECK(x.dim() == 4 && dy.dim() == 4,
+              "conv_depthwise: 4-D tensors only");
+  check_conv_operand(x, "x", "conv_depthwise");
+  check_conv_operand(dy, "dy", "conv_depthwise");
+  TORCH_CHECK(dy.device() == x.device(),
+              "conv_depthwise: dy must be on x's device");
+  const int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  TORCH_CHECK(dy.size(1) == C, "conv_depthwise: dy channels do not match x");
+  check_depthwise_shape(x, C, K, stride);
+  check_depthwise_shape(dy, C, K, stride);
+  check_conv_geometry("conv_depthwise", N, H, W, K, K, stride, K / 2);
+  check_conv_dy("conv_depthwise", dy, N, H, W, K, K, stride, K / 2);
+  const DwkPlan pl = dwk_plan(N, C, H, W, (int)K, (int)stride);
+  auto dw = torch::empty({C, 1, K, K}, x.options());
+  // per-block partial slabs, grown to need; every slab element the
+  // combine reads is written by the same call
+  static WsCache dws;
+  auto part = cached_ws(dws, x, at::kFloat, pl.part_floats);
+  launch_conv_depthwise_wgrad(pl, x.data_ptr(), dy.data_ptr(), dw.data_ptr(),
+                              part.data_ptr<float>(), N, C, H, W, (int)K,
+                              (int)stride, cur_stream());
+  return dw;
+}
+
+py::dict dwk_plan_py(int64_t N, int64_t C, int64_t H, int64_t W, int64_t K,
+                     int64_t stride) {
+  const DwkPlan pl = dwk_plan((int)N, (int)C, (int)H, (int)W, (int)K,
+                              (int)stride);
+  auto tiling = [](const DwkTiling& t) {
+    py::dict d;
+    d["tile"] = py::make_tuple(t.th, t.tw);
+    d["tiles"] = t.tiles;
+    d["slots"] = t.slots;
+    return d;
+  };
+  py::dict d;
+  d["V"] = pl.V;
+  d["chunk"] = pl.cc;
+  d["chunks"] = pl.nct;
+  d["fwd"] = tiling(pl.fwd);
+  d["dgrad"] = tiling(pl.dgrad);
+  d["wgrad"] = tiling(pl.wgrad);
+  d["part_floats"] = pl.part_floats;
+  return d;
+}
+
 // ---- NHWC max-pool ----------------------------------------------------
 std::vector<torch::Tensor> maxpool_fwd(torch::Tensor x, int64_t k,
                                        int64_t stride, int64_t pad) {
@@ -1347,6 +1465,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_grouped_wgrad", &conv_grouped_wgrad,
         "NHWC bf16 MFMA grouped 3x3 conv weight-grad (bf16 out, the "
         "weight's layout)");
+  m.def("conv_depthwise_fwd", &conv_depthwise_fwd,
+        "NHWC bf16 depthwise 3x3/5x5/7x7 conv forward (pad K/2)");
+  m.def("conv_depthwise_dgrad", &conv_depthwise_dgrad,
+        "NHWC bf16 depthwise conv data-grad");
+  m.def("conv_depthwise_wgrad", &conv_depthwise_wgrad,
+        "NHWC bf16 depthwise conv weight-grad (bf16 (C,1,K,K) out)");
+  m.def("dwk_plan", &dwk_plan_py,
+        "host decisions of the depthwise conv launchers for a shape");
   m.def("ce_fwd", &ce_fwd, "cross-entropy forward");
   m.def("ce_bwd", &ce_bwd, "cross-entropy backward");
   m.def("ls_ce_fwd", &ls_ce_fwd,

@@ -248,6 +248,42 @@ void launch_conv_grouped_wgrad(const void* x, const void* dy, void* dw,
 long conv_grouped_wgrad_part_floats(int N, int C, int Cg, int OH, int OW,
                                     int stride);
 
+// ---- conv_depthwise.hip: depthwise conv (groups == C), bf16 NHWC, square
+// K in {3, 5, 7}, pad K/2, stride 1 or 2, C % 4 == 0. w and dw are the
+// (C,1,K,K) weight, [C][K*K] in memory ------------------------------------
+// One direction's tiling: th x tw tiles of the tensor the kernel writes
+// (wgrad: of dy; stride-2 dgrad: of dx's (ih/2, iw/2) parity planes);
+// grid = slots * nct blocks, each walking its tiles grid-stride.
+struct DwkTiling {
+  int th, tw, tiles_h, tiles_w;
+  long tiles;  // N * tiles_h * tiles_w
+  int slots;   // blocks per channel chunk; wgrad: fp32 slabs to combine
+};
+// Every decision of one layer, taken once by dwk_plan (pure host code, no
+// device call; throws on an unsupported problem) and walked by the
+// launchers below.
+struct DwkPlan {
+  int V;        // channel vector: 8 (16-byte accesses) or 4 (C % 8 != 0)
+  int cc, nct;  // channels per block, channel chunks
+  int OH, OW;
+  DwkTiling fwd, dgrad, wgrad;
+  long part_floats;  // wgrad slab workspace: wgrad.slots * C * K * K
+};
+DwkPlan dwk_plan(int N, int C, int H, int W, int K, int stride);
+// N, C, H, W are x's in all three
+void launch_conv_depthwise_fwd(const DwkPlan&, const void* x, const void* w,
+                               void* y, int N, int C, int H, int W, int K,
+                               int stride, hipStream_t stream);
+void launch_conv_depthwise_dgrad(const DwkPlan&, const void* dy,
+                                 const void* w, void* dx, int N, int C, int H,
+                                 int W, int K, int stride,
+                                 hipStream_t stream);
+// part: plan.part_floats floats; dw: bf16, rounded once from the fp32 sum
+void launch_conv_depthwise_wgrad(const DwkPlan&, const void* x,
+                                 const void* dy, void* dw, float* part, int N,
+                                 int C, int H, int W, int K, int stride,
+                                 hipStream_t stream);
+
 // ---- maxpool.hip ------------------------------------------------------
 void launch_maxpool_fwd(const void*, void*, unsigned char*, int64_t,
                         int64_t, int, int, int, int, int, int, int,

@@ -27,6 +27,7 @@ KERNEL_SOURCES = [
     "attn_score.hip",
     "bindings.hip",
     "bn_act.hip",
+    "conv_depthwise.hip",
     "conv_grouped.hip",
     "conv_mfma.hip",
     "conv_mfma2.hip",
