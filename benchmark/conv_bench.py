@@ -23,7 +23,11 @@ directions, with each direction's share of its byte floor.
 
 ``--depthwise`` times NASNet-A mobile's 5x5 / 7x7 depthwise convs at
 ImageNet and CIFAR geometry (native csrc/conv_depthwise.hip vs the library)
-the same way."""
+the same way.
+
+``--line`` times the distinct (1,7) / (7,1) convs of inception3 at ImageNet
+and highres geometry (native csrc/conv_line.hip vs the library) in all three
+directions, with TFLOP/s of the native arm."""
 
 import argparse
 import json
@@ -286,6 +290,84 @@ def bench_depthwise(args):
         print(json.dumps(res), flush=True)
 
 
+def inception_line_shapes(batch):
+    """(dataset, batch, C, K, H, W, kernel_size) of every distinct (1,7) /
+    (7,1) conv inception3 runs at ImageNet and highres geometry, read off
+    one CPU forward of the model itself."""
+    import torch.nn as nn
+    from ddlbench_amd.config import DATASET_SHAPES
+    from ddlbench_amd.models import build_model
+    from ddlbench_amd.ops.conv import line_eligible
+    out = []
+    for dataset, n in (("imagenet", batch), ("highres", 32)):
+        model = build_model(dataset, "inception3").eval()
+
+        def hook(mod, inp, _out, dataset=dataset, n=n):
+            key = (dataset, n, mod.in_channels, mod.out_channels,
+                   inp[0].shape[2], inp[0].shape[3], mod.kernel_size)
+            if key not in out:
+                out.append(key)
+
+        for mod in model.modules():
+            if isinstance(mod, nn.Conv2d) and line_eligible(mod):
+                mod.register_forward_hook(hook)
+        C, H, W = DATASET_SHAPES[dataset][:3]
+        with torch.no_grad():
+            model(torch.zeros(1, C, H, W))
+    return out
+
+
+def bench_line(args):
+    """Native csrc/conv_line.hip against the library, all three directions,
+    alternating in one process."""
+    from ddlbench_amd.ops import require_extension
+    ext = require_extension()
+    dev = torch.device("cuda", 0)
+    cl = torch.channels_last
+    for dataset, N, C, K, H, W, ks in inception_line_shapes(args.batch):
+        pad = (ks[0] // 2, ks[1] // 2)
+        x = torch.randn(N, C, H, W, device=dev,
+                        dtype=torch.bfloat16).contiguous(memory_format=cl)
+        w = torch.randn(K, C, *ks, device=dev,
+                        dtype=torch.bfloat16).contiguous(memory_format=cl)
+        dy = torch.randn(N, K, H, W, device=dev,
+                         dtype=torch.bfloat16).contiguous(memory_format=cl)
+
+        def library_bwd(mask):
+            return torch.ops.aten.convolution_backward(
+                dy, x, w, None, [1, 1], list(pad), [1, 1], False, [0, 0], 1,
+                mask)
+
+        fns = {
+            "native_fwd": lambda: ext.conv_line_fwd(x, w),
+            "library_fwd": lambda: torch.nn.functional.conv2d(
+                x, w, None, 1, pad),
+            # the weight image is rebuilt every call, as in training
+            "native_dgrad": lambda: ext.conv_line_dgrad(
+                dy, ext.conv_weight_dgrad_layout(w), N, C, H, W),
+            "library_dgrad": lambda: library_bwd([True, False, False]),
+            "native_wgrad": lambda: ext.conv_line_wgrad(x, dy, *ks),
+            "library_wgrad": lambda: library_bwd([False, True, False]),
+        }
+        res = {"dataset": dataset,
+               "shape": f"C{C}_K{K}_H{H}_W{W}_k{ks[0]}x{ks[1]}", "batch": N}
+        # native and library alternate; two passes, the lower time counts
+        best = {}
+        for _ in range(2):
+            for name, fn in fns.items():
+                t = bench_op(fn, args.iters, args.warmup)
+                best[name] = min(best.get(name, t), t)
+        for name, t in best.items():
+            res[name + "_ms"] = round(t * 1e3, 4)
+        flops = 2.0 * N * H * W * K * C * ks[0] * ks[1]
+        for d in ("fwd", "dgrad", "wgrad"):
+            res[d + "_native_tf"] = round(flops / best["native_" + d] / 1e12,
+                                          1)
+            res[d + "_native_over_library"] = round(
+                best["native_" + d] / best["library_" + d], 3)
+        print(json.dumps(res), flush=True)
+
+
 def join_columns(ext, dy, w_perm, x, stride, pad, args):
     """dgrad+add: fused epilogue addend vs dgrad followed by a torch add
     (deep-pipeline structure; g stands in for the shortcut's gradient)."""
@@ -326,6 +408,9 @@ def main():
     p.add_argument("--depthwise", action="store_true",
                    help="time the 5x5/7x7 depthwise convs of nasnetamobile "
                         "(native vs library, fwd/dgrad/wgrad) instead")
+    p.add_argument("--line", action="store_true",
+                   help="time the (1,7)/(7,1) convs of inception3 (native "
+                        "vs library, fwd/dgrad/wgrad) instead")
     p.add_argument("--join", action="store_true",
                    help="per shape, only the data-grad and the dgrad+add "
                         "columns (fused addend vs dgrad then torch add)")
@@ -340,6 +425,9 @@ def main():
         return
     if args.depthwise:
         bench_depthwise(args)
+        return
+    if args.line:
+        bench_line(args)
         return
     from ddlbench_amd.ops.conv import conv2d_mfma
     dev = torch.device("cuda", 0)

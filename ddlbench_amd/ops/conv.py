@@ -23,6 +23,12 @@ data-grad and weight-grad kernels of csrc/conv_depthwise.hip through
 ``Conv2dDepthwise``. That choice is an argument only: no environment
 variable selects it.
 
+The (1,7) / (7,1) convs of Inception's factorised blocks (and (1,3) /
+(3,1)) are not square, so ``mfma_eligible`` leaves them to the library;
+``convert_convs(model, line="native")`` runs the forward, data-grad and
+weight-grad kernels of csrc/conv_line.hip through ``Conv2dLine``. Also an
+argument only.
+
 Every DDLB_* switch here is a row of ``ops.switches``: DDLB_CONV_TAIL is
 resolved once at import (``NATIVE_TAIL``), DDLB_JOIN per forward, and
 DDLB_STEM, DDLB_GROUPED and DDLB_MAXPOOL per ``convert_convs`` call."""
@@ -442,8 +448,76 @@ class Conv2dDepthwise(_NativeConv2d):
                         1, self.groups)
 
 
+class _ConvLine(torch.autograd.Function):
+    """(1,T) / (T,1) conv (stride 1, pad T/2 along the filter) on the
+    kernels of csrc/conv_line.hip: forward, data-grad (the forward kernel
+    on the (C,R,S,K) weight image, taps reversed) and weight-grad (bf16, in
+    the weight's layout), each backward direction only when its gradient is
+    needed."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        ext = _ops.require_extension()
+        x = x.contiguous(memory_format=_CL)
+        y = ext.conv_line_fwd(x, weight.contiguous(memory_format=_CL))
+        ctx.save_for_backward(x, weight)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        ext = _ops.require_extension()
+        x, weight = ctx.saved_tensors
+        dy = dy.contiguous(memory_format=_CL)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            w_perm = ext.conv_weight_dgrad_layout(
+                weight.contiguous(memory_format=_CL))
+            dx = ext.conv_line_dgrad(dy, w_perm, x.size(0), x.size(1),
+                                     x.size(2), x.size(3))
+        if ctx.needs_input_grad[1]:
+            dw = ext.conv_line_wgrad(x, dy, weight.shape[2], weight.shape[3])
+        return dx, dw
+
+
+def conv2d_line(x, weight):
+    return _ConvLine.apply(x, weight)
+
+
+def line_eligible(conv: nn.Conv2d, x_dtype=torch.bfloat16) -> bool:
+    """True for the problems csrc/conv_line.hip supports: a (1,T) or (T,1)
+    kernel with T in {3, 7}, padding T/2 along the filter and 0 across it,
+    stride 1, dilation 1, groups 1, no bias, C % 32 == 0 and K % 32 == 0.
+    (The line length, at most 64, is only known at run time; the binding
+    checks it.)"""
+    r, s = conv.kernel_size
+    return (x_dtype == torch.bfloat16
+            and conv.groups == 1
+            and conv.dilation == (1, 1)
+            and conv.bias is None
+            and conv.stride == (1, 1)
+            and (r, s) in ((1, 3), (3, 1), (1, 7), (7, 1))
+            and conv.padding == (r // 2, s // 2)
+            and conv.in_channels % 32 == 0
+            and conv.out_channels % 32 == 0)
+
+
+class Conv2dLine(_NativeConv2d):
+    """Drop-in for a line_eligible nn.Conv2d, running the line kernels."""
+
+    tag = "line"
+
+    def __init__(self, conv: nn.Conv2d):
+        super().__init__(conv)
+        self.stride = conv.stride
+        self.padding = conv.padding
+
+    def native(self, x):
+        return conv2d_line(x, self.weight)
+
+
 def convert_convs(model: nn.Module, dtype=torch.bfloat16,
-                  stem=None, grouped=None, depthwise="library") -> int:
+                  stem=None, grouped=None, depthwise="library",
+                  line="library") -> int:
     """Replace eligible nn.Conv2d children with Conv2dMFMA and eligible
     nn.MaxPool2d with the native NHWC pool. Returns the number of
     conversions.
@@ -454,10 +528,12 @@ def convert_convs(model: nn.Module, dtype=torch.bfloat16,
     time. ``grouped`` does the same for grouped_eligible 3x3 convs
     (Conv2dGrouped, DDLB_GROUPED). ``depthwise="native"`` swaps
     depthwise_eligible convs for Conv2dDepthwise; it has no environment
-    variable and defaults to "library"."""
+    variable and defaults to "library". ``line="native"`` does the same
+    for line_eligible (1,T) / (T,1) convs (Conv2dLine)."""
     stem = resolve("stem", stem)
     grouped = resolve("grouped", grouped)
     check("depthwise", depthwise, ("native", "library"))
+    check("line", line, ("native", "library"))
     count = 0
     for parent in model.modules():
         for name, child in list(parent.named_children()):
@@ -474,6 +550,9 @@ def convert_convs(model: nn.Module, dtype=torch.bfloat16,
                 count += 1
             elif depthwise == "native" and depthwise_eligible(child, dtype):
                 setattr(parent, name, Conv2dDepthwise(child))
+                count += 1
+            elif line == "native" and line_eligible(child, dtype):
+                setattr(parent, name, Conv2dLine(child))
                 count += 1
     if dtype == torch.bfloat16 and enabled("maxpool"):
         from ddlbench_amd.ops.pool import convert_maxpools

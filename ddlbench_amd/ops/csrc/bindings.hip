@@ -1297,6 +1297,130 @@ py::dict dwk_plan_py(int64_t N, int64_t C, int64_t H, int64_t W, int64_t K,
   return d;
 }
 
+// ---- line conv: (1,T) / (T,1), NHWC bf16 -------------------------------
+// Supported problem of csrc/conv_line.hip; a violation raises before any
+// launch. (R, S) is the filter; returns 1 for (T,1), 0 for (1,T).
+static int check_line_shape(int64_t C, int64_t K, int64_t H, int64_t W,
+                            int64_t R, int64_t S) {
+  TORCH_CHECK((R == 1) != (S == 1),
+              "conv_line needs a (1,T) or (T,1) kernel");
+  const int64_t T = R * S;
+  TORCH_CHECK(T == 3 || T == 7, "conv_line needs a filter of 3 or 7 taps");
+  TORCH_CHECK(C >= 32 && C % 32 == 0 && K >= 32 && K % 32 == 0,
+              "conv_line needs C % 32 == 0 and K % 32 == 0");
+  const int orient_h = S == 1;
+  TORCH_CHECK((orient_h ? H : W) <= 64,
+              "conv_line needs a line length of at most 64");
+  return orient_h;
+}
+
+static void check_line_operand(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(t.dim() == 4, "conv_line: 4-D tensors only");
+  check_conv_operand(t, name, "conv_line");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+              "conv_line: tensors must be 16-byte aligned");
+}
+
+// x: (N,C,H,W) channels_last; w: (K,C,1,T) or (K,C,T,1) channels_last; pad
+// T/2 along the filter. Returns channels_last y (N,K,H,W).
+torch::Tensor conv_line_fwd(torch::Tensor x, torch::Tensor w) {
+  check_line_operand(x, "x");
+  check_line_operand(w, "w");
+  TORCH_CHECK(w.device() == x.device(),
+              "conv_line: w must be on the input's device");
+  const int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  const int K = w.size(0);
+  TORCH_CHECK(w.size(1) == C, "conv_line: w channels do not match x");
+  const int oh = check_line_shape(C, K, H, W, w.size(2), w.size(3));
+  const int T = (int)(w.size(2) * w.size(3));
+  const LinePlan pl = line_plan(N, C, K, H, W, oh, T);
+  auto y = empty_nhwc(x, N, K, H, W);
+  launch_conv_line_fwd(pl, x.data_ptr(), w.data_ptr(), y.data_ptr(), N, C, K,
+                       H, W, oh, T, cur_stream());
+  return y;
+}
+
+// dy: (N,K,H,W) channels_last; w_crsk: the contiguous (C,R,S,K) image that
+// conv_weight_dgrad_layout makes. Returns channels_last dx (N,C,H,W).
+torch::Tensor conv_line_dgrad(torch::Tensor dy, torch::Tensor w_crsk,
+                              int64_t N, int64_t C, int64_t H, int64_t W) {
+  check_line_operand(dy, "dy");
+  TORCH_CHECK(w_crsk.is_cuda() && w_crsk.scalar_type() == at::kBFloat16 &&
+                  w_crsk.device() == dy.device() && w_crsk.dim() == 4 &&
+                  w_crsk.is_contiguous(),
+              "conv_line: w must be a contiguous bf16 (C,R,S,K) tensor on "
+              "dy's device");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(w_crsk.data_ptr()) % 16 == 0,
+              "conv_line: tensors must be 16-byte aligned");
+  const int64_t K = dy.size(1);
+  TORCH_CHECK(w_crsk.size(0) == C && w_crsk.size(3) == K,
+              "conv_line: w does not match (C, K)");
+  TORCH_CHECK(N >= 1 && H >= 1 && W >= 1, "conv_line: empty input");
+  const int oh = check_line_shape(C, K, H, W, w_crsk.size(1), w_crsk.size(2));
+  TORCH_CHECK(dy.size(0) == N && dy.size(2) == H && dy.size(3) == W,
+              "conv_line: dy does not match (N, H, W)");
+  const int T = (int)(w_crsk.size(1) * w_crsk.size(2));
+  const LinePlan pl = line_plan((int)N, (int)C, (int)K, (int)H, (int)W, oh, T);
+  auto dx = empty_nhwc(dy, N, C, H, W);
+  launch_conv_line_dgrad(pl, dy.data_ptr(), w_crsk.data_ptr(), dx.data_ptr(),
+                         (int)N, (int)C, (int)K, (int)H, (int)W, oh, T,
+                         cur_stream());
+  return dx;
+}
+
+// x: (N,C,H,W), dy: (N,K,H,W), both channels_last; (R,S) the filter.
+// Returns bf16 dw of logical shape (K,C,R,S) with channels_last strides,
+// each element the round-to-nearest-even bf16 of its fp32 sum.
+torch::Tensor conv_line_wgrad(torch::Tensor x, torch::Tensor dy, int64_t R,
+                              int64_t S) {
+  check_line_operand(x, "x");
+  check_line_operand(dy, "dy");
+  TORCH_CHECK(dy.device() == x.device(),
+              "conv_line: dy must be on x's device");
+  const int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  const int K = dy.size(1);
+  const int oh = check_line_shape(C, K, H, W, R, S);
+  TORCH_CHECK(dy.size(0) == N && dy.size(2) == H && dy.size(3) == W,
+              "conv_line: dy does not match (N, H, W)");
+  const int T = (int)(R * S);
+  const LinePlan pl = line_plan(N, C, K, H, W, oh, T);
+  auto dw = torch::empty({K, R, S, C}, x.options()).permute({0, 3, 1, 2});
+  // per-block partial slabs, grown to need; every slab element the
+  // combine reads is written by the same call
+  static WsCache lws;
+  auto part = cached_ws(lws, x, at::kFloat, pl.part_floats);
+  launch_conv_line_wgrad(pl, x.data_ptr(), dy.data_ptr(), dw.data_ptr(),
+                         part.data_ptr<float>(), N, C, K, H, W, oh, T,
+                         cur_stream());
+  return dw;
+}
+
+py::dict line_plan_py(int64_t N, int64_t C, int64_t K, int64_t H, int64_t W,
+                      const std::string& orient, int64_t T) {
+  TORCH_CHECK(orient == "w" || orient == "h",
+              "line_plan: orient is \"w\" for (1,T) or \"h\" for (T,1)");
+  const LinePlan pl = line_plan((int)N, (int)C, (int)K, (int)H, (int)W,
+                                orient == "h", (int)T);
+  auto tiling = [](const LineTiling& t) {
+    py::dict d;
+    d["grid"] = py::make_tuple(t.ntm, t.ntn);
+    d["tiles"] = t.tiles;
+    d["slots"] = t.slots;
+    return d;
+  };
+  py::dict d;
+  d["L"] = pl.L;
+  d["lines"] = pl.nlines;
+  d["BL"] = pl.BL;
+  d["wgrad_lines_per_step"] = pl.BLW;
+  d["wgrad_slots_per_step"] = pl.SP;
+  d["fwd"] = tiling(pl.fwd);
+  d["dgrad"] = tiling(pl.dgrad);
+  d["wgrad"] = tiling(pl.wgrad);
+  d["part_floats"] = pl.part_floats;
+  return d;
+}
+
 // ---- NHWC max-pool ----------------------------------------------------
 std::vector<torch::Tensor> maxpool_fwd(torch::Tensor x, int64_t k,
                                        int64_t stride, int64_t pad) {
@@ -1473,6 +1597,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "NHWC bf16 depthwise conv weight-grad (bf16 (C,1,K,K) out)");
   m.def("dwk_plan", &dwk_plan_py,
         "host decisions of the depthwise conv launchers for a shape");
+  m.def("conv_line_fwd", &conv_line_fwd,
+        "NHWC bf16 (1,T)/(T,1) conv forward, T in {3,7}, pad T/2");
+  m.def("conv_line_dgrad", &conv_line_dgrad,
+        "NHWC bf16 (1,T)/(T,1) conv data-grad on the (C,R,S,K) weight image");
+  m.def("conv_line_wgrad", &conv_line_wgrad,
+        "NHWC bf16 (1,T)/(T,1) conv weight-grad (bf16 channels_last out)");
+  m.def("line_plan", &line_plan_py,
+        "host decisions of the line conv launchers for a shape");
   m.def("ce_fwd", &ce_fwd, "cross-entropy forward");
   m.def("ce_bwd", &ce_bwd, "cross-entropy backward");
   m.def("ls_ce_fwd", &ls_ce_fwd,

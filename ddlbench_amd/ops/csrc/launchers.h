@@ -284,6 +284,44 @@ void launch_conv_depthwise_wgrad(const DwkPlan&, const void* x,
                                  int C, int H, int W, int K, int stride,
                                  hipStream_t stream);
 
+// ---- conv_line.hip: (1,T) / (T,1) conv, bf16 NHWC, T in {3, 7}, stride 1,
+// pad T/2 along the filter, C % 32 == 0, K % 32 == 0, line length <= 64.
+// orient_h = 0: (1,T), a line is an image row; 1: (T,1), an image column ---
+// fwd / dgrad: ntm row tiles of BL lines x ntn column tiles of 64 channels,
+// `slots` blocks walking `tiles` grid-stride. wgrad: ntm x ntn dW tiles of
+// 64 x 64, `tiles` steps of BLW lines shared out over `slots` fp32 slabs.
+struct LineTiling {
+  int ntm, ntn;
+  long tiles;
+  int slots;
+};
+// Every decision of one layer, taken once by line_plan (pure host code, no
+// device call; throws on an unsupported problem).
+struct LinePlan {
+  int L;        // line length
+  long nlines;
+  int BL;       // fwd / dgrad: lines per tile
+  int BLW, SP;  // wgrad: lines and padded slots per step
+  int steps_per;  // wgrad: steps per slab
+  LineTiling fwd, dgrad, wgrad;
+  long part_floats;  // wgrad slab workspace: wgrad.slots * K * T * C
+};
+LinePlan line_plan(int N, int C, int K, int H, int W, int orient_h, int T);
+// N, C, H, W are x's in all three; w is the (K,R,S,C) channels_last weight
+// memory, w_crsk the (C,R,S,K) image of conv_weight_dgrad_layout
+void launch_conv_line_fwd(const LinePlan&, const void* x, const void* w,
+                          void* y, int N, int C, int K, int H, int W,
+                          int orient_h, int T, hipStream_t stream);
+void launch_conv_line_dgrad(const LinePlan&, const void* dy,
+                            const void* w_crsk, void* dx, int N, int C, int K,
+                            int H, int W, int orient_h, int T,
+                            hipStream_t stream);
+// part: plan.part_floats floats; dw: bf16 (K,T,C) memory, rounded once from
+// the fp32 sum
+void launch_conv_line_wgrad(const LinePlan&, const void* x, const void* dy,
+                            void* dw, float* part, int N, int C, int K, int H,
+                            int W, int orient_h, int T, hipStream_t stream);
+
 // ---- maxpool.hip ------------------------------------------------------
 void launch_maxpool_fwd(const void*, void*, unsigned char*, int64_t,
                         int64_t, int, int, int, int, int, int, int,

@@ -29,6 +29,7 @@ KERNEL_SOURCES = [
     "bn_act.hip",
     "conv_depthwise.hip",
     "conv_grouped.hip",
+    "conv_line.hip",
     "conv_mfma.hip",
     "conv_mfma2.hip",
     "conv_stem.hip",
