@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Fused-op microbenchmarks vs eager PyTorch: BN+ReLU(+add), CE,
-label-smoothed CE, attention score, attention context, LSTM, SGD (--ops
-picks arms).
+label-smoothed CE, attention score, attention context, LSTM, SGD, average
+pools (--ops picks arms).
 
 Reports ms and achieved HBM GB/s per op over ResNet-50 activation
 shapes in both layouts — the evidence for the memory-bound fusion wins
@@ -295,6 +295,131 @@ def bench_lstm(dev, iters, warmup, rounds=5):
         del m, x, dy, hx
 
 
+# (name, N, C, H, W, (k, stride, pad) or None for the global pool): the
+# average pools of the model zoo at batch 256
+AVGPOOL_SHAPES = [
+    ("inception A 35", 256, 288, 35, 35, (3, 1, 1)),
+    ("inception C 17", 256, 768, 17, 17, (3, 1, 1)),
+    ("nasnet normal 112", 256, 44, 112, 112, (3, 1, 1)),
+    ("nasnet normal 56", 256, 88, 56, 56, (3, 1, 1)),
+    ("nasnet normal 28", 256, 176, 28, 28, (3, 1, 1)),
+    ("nasnet reduction 112", 256, 88, 112, 112, (3, 2, 1)),
+    ("nasnet reduction 56", 256, 176, 56, 56, (3, 2, 1)),
+    ("densenet transition 56", 256, 128, 56, 56, (2, 2, 0)),
+    ("densenet transition 28", 256, 256, 28, 28, (2, 2, 0)),
+    ("densenet transition 14", 256, 512, 14, 14, (2, 2, 0)),
+    ("head resnet50", 256, 2048, 7, 7, None),
+    ("head mobilenetv2", 256, 1280, 7, 7, None),
+    ("head inception 8", 256, 768, 8, 8, None),
+    ("head resnet50 highres", 64, 2048, 16, 16, None),
+]
+STREAM_BYTES_PER_S = 6.29e12   # measured streaming rate (profiles/)
+
+
+def bench_avgpool(dev, iters, warmup, rounds=3):
+    """Average pools, bf16 channels_last: the native kernels (ext calls)
+    against the library (F.avg_pool2d / F.adaptive_avg_pool2d and their
+    autograd), forward and backward separately, alternated in rounds in one
+    process. share = byte floor (x + y once at the streaming rate) / native
+    time. Then an Inception-v3 and a NASNet-A training step with
+    convert_convs(avgpool="library") against "native", alternated."""
+    import torch.nn.functional as F
+    from ddlbench_amd.ops import require_extension
+    ext = require_extension()
+    cl = torch.channels_last
+    for name, N, C, H, W, geom in AVGPOOL_SHAPES:
+        g = torch.Generator(device=dev).manual_seed(C * H)
+        x = torch.randn(N, C, H, W, device=dev, dtype=torch.bfloat16,
+                        generator=g).contiguous(memory_format=cl)
+        xl = x.clone().requires_grad_(True)
+        yl = F.avg_pool2d(xl, *geom) if geom \
+            else F.adaptive_avg_pool2d(xl, 1)
+        dy = torch.randn_like(yl).contiguous(memory_format=cl)
+        arms = {
+            "fwd": {"native": (lambda: ext.avgpool_fwd(x, *geom)) if geom
+                    else (lambda: ext.global_avgpool_fwd(x)),
+                    "library": (lambda: F.avg_pool2d(x, *geom)) if geom
+                    else (lambda: F.adaptive_avg_pool2d(x, 1))},
+            "bwd": {"native": (lambda: ext.avgpool_bwd(dy, H, W, *geom))
+                    if geom else (lambda: ext.global_avgpool_bwd(dy, H, W)),
+                    "library": lambda: torch.autograd.grad(
+                        yl, xl, dy, retain_graph=True)},
+        }
+        floor = (x.numel() + yl.numel()) * 2 / STREAM_BYTES_PER_S
+        for direction, fns in arms.items():
+            times = {"native": [], "library": []}
+            for _ in range(rounds):
+                for arm, fn in fns.items():
+                    times[arm].append(timeit(fn, iters, warmup))
+            best = {a: min(v) for a, v in times.items()}
+            print(json.dumps({
+                "op": f"avgpool_{direction}", "layer": name,
+                "shape": f"{N}x{C}x{H}x{W}",
+                "geom": list(geom) if geom else "global",
+                "native_ms": round(best["native"] * 1e3, 4),
+                "library_ms": round(best["library"] * 1e3, 4),
+                "ratio": round(best["native"] / best["library"], 2),
+                "floor_ms": round(floor * 1e3, 4),
+                "share": round(floor / best["native"], 2)}), flush=True)
+        del x, xl, yl, dy, arms
+    bench_avgpool_step(dev)
+
+
+def bench_avgpool_step(dev, batch=256, rounds=4, steps=3, warmup=3):
+    """Training step (forward, native cross-entropy, backward, fused SGD),
+    ImageNet shape, bf16: two models that differ only in avgpool=, rounds of
+    `steps` steps per arm alternating after `warmup` steps each, every step
+    timed by a host clock between device synchronises."""
+    from ddlbench_amd.models import build_model
+    from ddlbench_amd.ops import functional as NF
+    from ddlbench_amd.ops.conv import convert_convs
+    from ddlbench_amd.ops.sgd import FusedSGD
+    cl = torch.channels_last
+    for arch in ("inception3", "nasnetamobile"):
+        torch.manual_seed(0)
+        x = torch.randn(batch, 3, 224, 224, device=dev,
+                        dtype=torch.bfloat16).contiguous(memory_format=cl)
+        t = torch.randint(1000, (batch,), device=dev)
+        runs = {}
+        for mode in ("library", "native"):
+            torch.manual_seed(1)
+            m = build_model("imagenet", arch).to(dev).to(torch.bfloat16) \
+                .to(memory_format=cl)
+            n = convert_convs(m, depthwise="native", line="native",
+                              avgpool=mode)
+            opt = FusedSGD(m.parameters(), lr=0.01, momentum=0.9,
+                           backend="native")
+            runs[mode] = (m, opt, n)
+
+        def step(mode):
+            m, opt, _ = runs[mode]
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            loss = NF.cross_entropy(m(x), t, backend="native")
+            opt.zero_grad(set_to_none=True)
+            loss.backward()
+            opt.step()
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0
+
+        times = {mode: [] for mode in runs}
+        for mode in runs:
+            for _ in range(warmup):
+                step(mode)
+        for _ in range(rounds):
+            for mode in runs:
+                times[mode] += [step(mode) for _ in range(steps)]
+        row = {"op": "avgpool_train_step", "arch": arch, "batch": batch}
+        for mode, v in times.items():
+            v = sorted(v)
+            row[mode] = {"converted": runs[mode][2],
+                         "median_ms": round(v[len(v) // 2] * 1e3, 2),
+                         "min_ms": round(v[0] * 1e3, 2),
+                         "max_ms": round(v[-1] * 1e3, 2), "steps": len(v)}
+        print(json.dumps(row), flush=True)
+        del runs, x
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--iters", type=int, default=20)
@@ -302,11 +427,12 @@ def main():
     p.add_argument("--dtype", default="bfloat16")
     p.add_argument("--ops", default="bn,ce,ls_ce,attn,attn_ctx,lstm,sgd",
                    help="comma-separated arms: bn, ce, ls_ce, attn, "
-                        "attn_ctx, lstm, sgd")
+                        "attn_ctx, lstm, sgd, avgpool (avgpool is not in "
+                        "the default set: it ends in four training runs)")
     args = p.parse_args()
     arms = set(args.ops.split(","))
     assert arms <= {"bn", "ce", "ls_ce", "attn", "attn_ctx", "lstm",
-                    "sgd"}, args.ops
+                    "sgd", "avgpool"}, args.ops
     assert torch.cuda.is_available()
     from ddlbench_amd.ops import functional as NF
     dev = torch.device("cuda", 0)
@@ -409,6 +535,9 @@ def main():
 
     if "lstm" in arms:
         bench_lstm(dev, args.iters, args.warmup)
+
+    if "avgpool" in arms:
+        bench_avgpool(dev, args.iters, args.warmup)
 
     if "sgd" not in arms:
         return

@@ -53,9 +53,10 @@ class Transition(nn.Module):
         super().__init__()
         self.bn = BNAct(cin, act="relu")
         self.conv = nn.Conv2d(cin, cout, 1, bias=False)
+        self.pool = nn.AvgPool2d(2)
 
     def forward(self, x):
-        return F.avg_pool2d(self.conv(self.bn(x)), 2)
+        return self.pool(self.conv(self.bn(x)))
 
 
 _DENSENET_CFG = {
@@ -87,25 +88,31 @@ class DenseNet(nn.Module):
                 c //= 2
         mods.append(BNAct(c, act="relu"))
         self.features = nn.Sequential(*mods)
+        self.pool = nn.AdaptiveAvgPool2d(1)
         self.classifier = nn.Linear(c, num_classes)
 
     def forward(self, x):
         x = self.features(x)
-        x = F.adaptive_avg_pool2d(x, 1).flatten(1)
+        x = self.pool(x).flatten(1)
         return self.classifier(x)
 
     def to_sequential(self) -> nn.Sequential:
         return nn.Sequential(*self.features,
-                             _PoolFC(self.classifier))
+                             _PoolFC(self.classifier, self.pool))
 
 
 class _PoolFC(nn.Module):
-    def __init__(self, fc):
+    """Global average pool + classifier. The pool is a parameter-free child
+    (shared with the owning model when it passes its own), so
+    ``convert_avgpools`` can swap it."""
+
+    def __init__(self, fc, pool=None):
         super().__init__()
+        self.pool = pool if pool is not None else nn.AdaptiveAvgPool2d(1)
         self.fc = fc
 
     def forward(self, x):
-        return self.fc(F.adaptive_avg_pool2d(x, 1).flatten(1))
+        return self.fc(self.pool(x).flatten(1))
 
 
 # ------------------------------------------------------------ Inception
@@ -132,11 +139,12 @@ class InceptionA(nn.Module):
         self.b3 = nn.Sequential(_CBR(cin, 64, 1),
                                 _CBR(64, 96, 3, padding=1),
                                 _CBR(96, 96, 3, padding=1))
+        self.pool = nn.AvgPool2d(3, 1, 1)
         self.bp = _CBR(cin, pool_features, 1)
         self.out_channels = 64 + 64 + 96 + pool_features
 
     def forward(self, x):
-        pool = self.bp(F.avg_pool2d(x, 3, stride=1, padding=1))
+        pool = self.bp(self.pool(x))
         return torch.cat([self.b1(x), self.b5(x), self.b3(x), pool], 1)
 
 
@@ -170,11 +178,12 @@ class InceptionC(nn.Module):
             _CBR(ch7, ch7, (1, 7), padding=(0, 3)),
             _CBR(ch7, ch7, (7, 1), padding=(3, 0)),
             _CBR(ch7, 192, (1, 7), padding=(0, 3)))
+        self.pool = nn.AvgPool2d(3, 1, 1)
         self.bp = _CBR(cin, 192, 1)
         self.out_channels = 192 * 4
 
     def forward(self, x):
-        pool = self.bp(F.avg_pool2d(x, 3, stride=1, padding=1))
+        pool = self.bp(self.pool(x))
         return torch.cat([self.b1(x), self.b7(x), self.b7d(x), pool], 1)
 
 
@@ -196,15 +205,17 @@ class Inception3(nn.Module):
         c2 = InceptionC(c1.out_channels, 160)
         c3 = InceptionC(c2.out_channels, 192)
         self.blocks = nn.Sequential(a1, a2, a3, b, c1, c2, c3)
+        self.pool = nn.AdaptiveAvgPool2d(1)
         self.fc = nn.Linear(c3.out_channels, num_classes)
 
     def forward(self, x):
         x = self.blocks(self.stem(x))
-        x = F.adaptive_avg_pool2d(x, 1).flatten(1)
+        x = self.pool(x).flatten(1)
         return self.fc(x)
 
     def to_sequential(self) -> nn.Sequential:
-        return nn.Sequential(self.stem, *self.blocks, _PoolFC(self.fc))
+        return nn.Sequential(self.stem, *self.blocks,
+                             _PoolFC(self.fc, self.pool))
 
 
 # ------------------------------------------------------------ SqueezeNet
@@ -239,22 +250,25 @@ class SqueezeNet(nn.Module):
             Fire(256, 48, 192, 192), Fire(384, 48, 192, 192),
             Fire(384, 64, 256, 256), Fire(512, 64, 256, 256))
         self.classifier_conv = nn.Conv2d(512, num_classes, 1)
+        self.pool = nn.AdaptiveAvgPool2d(1)
 
     def forward(self, x):
         x = F.relu(self.classifier_conv(self.features(x)), inplace=True)
-        return F.adaptive_avg_pool2d(x, 1).flatten(1)
+        return self.pool(x).flatten(1)
 
     def to_sequential(self) -> nn.Sequential:
         class _Head(nn.Module):
-            def __init__(self, conv):
+            def __init__(self, conv, pool):
                 super().__init__()
                 self.conv = conv
+                self.pool = pool
 
             def forward(self, x):
                 x = F.relu(self.conv(x), inplace=True)
-                return F.adaptive_avg_pool2d(x, 1).flatten(1)
+                return self.pool(x).flatten(1)
 
-        return nn.Sequential(*self.features, _Head(self.classifier_conv))
+        return nn.Sequential(*self.features,
+                             _Head(self.classifier_conv, self.pool))
 
 
 # ----------------------------------------------------------- MobileNetV1
@@ -287,12 +301,13 @@ class MobileNetV1(nn.Module):
             mods.append(DWSeparable(c, cout, s))
             c = cout
         self.features = nn.Sequential(*mods)
+        self.pool = nn.AdaptiveAvgPool2d(1)
         self.fc = nn.Linear(1024, num_classes)
 
     def forward(self, x):
         x = self.features(x)
-        x = F.adaptive_avg_pool2d(x, 1).flatten(1)
+        x = self.pool(x).flatten(1)
         return self.fc(x)
 
     def to_sequential(self) -> nn.Sequential:
-        return nn.Sequential(*self.features, _PoolFC(self.fc))
+        return nn.Sequential(*self.features, _PoolFC(self.fc, self.pool))

@@ -12,7 +12,6 @@ projection-BN + residual-add are fused BNAct calls."""
 from __future__ import annotations
 
 import torch.nn as nn
-import torch.nn.functional as F
 
 from ddlbench_amd.ops.modules import BNAct, DepthwiseConv3x3
 
@@ -73,12 +72,13 @@ class _LastConv(nn.Module):
 
 
 class _Head(nn.Module):
-    def __init__(self, fc):
+    def __init__(self, fc, pool):
         super().__init__()
+        self.pool = pool
         self.fc = fc
 
     def forward(self, x):
-        return self.fc(F.adaptive_avg_pool2d(x, 1).flatten(1))
+        return self.fc(self.pool(x).flatten(1))
 
 
 class MobileNetV2(nn.Module):
@@ -95,12 +95,14 @@ class MobileNetV2(nn.Module):
                 cin = c
         features.append(_LastConv(cin, 1280))
         self.features = nn.Sequential(*features)
+        self.pool = nn.AdaptiveAvgPool2d(1)
         self.classifier = nn.Linear(1280, num_classes)
 
     def forward(self, x):
         x = self.features(x)
-        x = F.adaptive_avg_pool2d(x, 1).flatten(1)
+        x = self.pool(x).flatten(1)
         return self.classifier(x)
 
     def to_sequential(self) -> nn.Sequential:
-        return nn.Sequential(*self.features, _Head(self.classifier))
+        return nn.Sequential(*self.features,
+                             _Head(self.classifier, self.pool))

@@ -79,6 +79,7 @@ class NormalCell(nn.Module):
         self.b1_r = SepConv(planes, planes, 5, 1)
         self.b2_r = SepConv(planes, planes, 5, 1)   # avg(h) + sep5(hp)
         self.b4_l = SepConv(planes, planes, 3, 1)
+        self.pool = nn.AvgPool2d(3, 1, 1)   # one instance, three calls
         self.out_channels = 5 * planes
 
     def forward(self, h, hp):
@@ -86,8 +87,8 @@ class NormalCell(nn.Module):
         xp = self.fit_hp(hp)
         b0 = self.b0_l(x) + x
         b1 = self.b1_l(xp) + self.b1_r(x)
-        b2 = F.avg_pool2d(x, 3, 1, 1) + self.b2_r(xp)
-        b3 = F.avg_pool2d(xp, 3, 1, 1) + F.avg_pool2d(xp, 3, 1, 1)
+        b2 = self.pool(x) + self.b2_r(xp)
+        b3 = self.pool(xp) + self.pool(xp)
         b4 = self.b4_l(xp) + xp
         return torch.cat([b0, b1, b2, b3, b4], 1)
 
@@ -105,6 +106,8 @@ class ReductionCell(nn.Module):
         self.b1_r = SepConv(planes, planes, 7, 2)
         self.b2_r = SepConv(planes, planes, 5, 2)
         self.b4_l = SepConv(planes, planes, 3, 1)
+        self.pool_s2 = nn.AvgPool2d(3, 2, 1)
+        self.pool = nn.AvgPool2d(3, 1, 1)
         self.out_channels = 4 * planes
 
     def forward(self, h, hp):
@@ -112,9 +115,9 @@ class ReductionCell(nn.Module):
         xp = self.fit_hp(hp)
         b0 = self.b0_l(xp) + self.b0_r(x)
         b1 = F.max_pool2d(x, 3, 2, 1) + self.b1_r(xp)
-        b2 = F.avg_pool2d(x, 3, 2, 1) + self.b2_r(xp)
+        b2 = self.pool_s2(x) + self.b2_r(xp)
         b3 = F.max_pool2d(x, 3, 2, 1) + self.b4_l(b0)
-        b4 = F.avg_pool2d(b0, 3, 1, 1) + b1
+        b4 = self.pool(b0) + b1
         return torch.cat([b1, b2, b3, b4], 1)
 
 
@@ -157,6 +160,7 @@ class NASNetAMobile(nn.Module):
                 c_h, c_hp = cell.out_channels, c_h
                 hp_reduced = False
         self.cells = nn.ModuleList(cells)
+        self.pool = nn.AdaptiveAvgPool2d(1)
         self.fc = nn.Linear(c_h, num_classes)
 
     def forward(self, x):
@@ -165,7 +169,7 @@ class NASNetAMobile(nn.Module):
         for cell in self.cells:
             h, hp = cell(h, hp), h
         h = F.relu(h)
-        h = F.adaptive_avg_pool2d(h, 1).flatten(1)
+        h = self.pool(h).flatten(1)
         return self.fc(h)
 
     def to_sequential(self) -> nn.Sequential:
@@ -180,15 +184,16 @@ class NASNetAMobile(nn.Module):
                 return h, h
 
         class _Head(nn.Module):
-            def __init__(self, fc):
+            def __init__(self, fc, pool):
                 super().__init__()
+                self.pool = pool
                 self.fc = fc
 
             def forward(self, state):
                 h, _ = state
-                h = F.adaptive_avg_pool2d(F.relu(h), 1).flatten(1)
+                h = self.pool(F.relu(h)).flatten(1)
                 return self.fc(h)
 
         return nn.Sequential(_Stem(self.stem_conv, self.stem_bn),
                              *[_CellChainUnit(c) for c in self.cells],
-                             _Head(self.fc))
+                             _Head(self.fc, self.pool))

@@ -517,7 +517,7 @@ class Conv2dLine(_NativeConv2d):
 
 def convert_convs(model: nn.Module, dtype=torch.bfloat16,
                   stem=None, grouped=None, depthwise="library",
-                  line="library") -> int:
+                  line="library", avgpool="library") -> int:
     """Replace eligible nn.Conv2d children with Conv2dMFMA and eligible
     nn.MaxPool2d with the native NHWC pool. Returns the number of
     conversions.
@@ -529,11 +529,14 @@ def convert_convs(model: nn.Module, dtype=torch.bfloat16,
     (Conv2dGrouped, DDLB_GROUPED). ``depthwise="native"`` swaps
     depthwise_eligible convs for Conv2dDepthwise; it has no environment
     variable and defaults to "library". ``line="native"`` does the same
-    for line_eligible (1,T) / (T,1) convs (Conv2dLine)."""
+    for line_eligible (1,T) / (T,1) convs (Conv2dLine), and
+    ``avgpool="native"`` for avgpool_eligible nn.AvgPool2d /
+    nn.AdaptiveAvgPool2d(1) children (ops.pool.convert_avgpools)."""
     stem = resolve("stem", stem)
     grouped = resolve("grouped", grouped)
     check("depthwise", depthwise, ("native", "library"))
     check("line", line, ("native", "library"))
+    check("avgpool", avgpool, ("native", "library"))
     count = 0
     for parent in model.modules():
         for name, child in list(parent.named_children()):
@@ -557,4 +560,7 @@ def convert_convs(model: nn.Module, dtype=torch.bfloat16,
     if dtype == torch.bfloat16 and enabled("maxpool"):
         from ddlbench_amd.ops.pool import convert_maxpools
         count += convert_maxpools(model)
+    if dtype == torch.bfloat16 and avgpool == "native":
+        from ddlbench_amd.ops.pool import convert_avgpools
+        count += convert_avgpools(model)
     return count

@@ -1462,6 +1462,125 @@ torch::Tensor maxpool_bwd(torch::Tensor dy, torch::Tensor idx,
   return dx;
 }
 
+// ---- NHWC average pool ------------------------------------------------
+// Operand contract of csrc/avgpool.hip; a violation raises before any
+// launch.
+static void check_avgpool_operand(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(t.dim() == 4, "avgpool: 4-D tensors only");
+  check_conv_operand(t, name, "avgpool");
+  const int64_t C = t.size(1);
+  TORCH_CHECK(C >= 4 && C % 4 == 0, "avgpool needs C % 4 == 0");
+  TORCH_CHECK(t.size(0) >= 1 && t.size(2) >= 1 && t.size(3) >= 1,
+              "avgpool: empty input");
+  TORCH_CHECK(t.numel() < (int64_t(1) << 40) && t.size(0) < (1 << 30) &&
+                  t.size(2) < (1 << 15) && t.size(3) < (1 << 15),
+              "avgpool: tensor too large");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) %
+                      (C % 8 == 0 ? 16 : 8) == 0,
+              "avgpool: tensors must be aligned to their channel vector");
+}
+
+static void check_avgpool_window(int64_t k, int64_t stride, int64_t pad) {
+  TORCH_CHECK((k == 3 && stride == 1 && pad == 1) ||
+                  (k == 3 && stride == 2 && pad == 1) ||
+                  (k == 2 && stride == 2 && pad == 0),
+              "avgpool supports (k, stride, pad) in {(3,1,1), (3,2,1), "
+              "(2,2,0)}");
+}
+
+// x: (N,C,H,W) channels_last. Returns channels_last y, the average over
+// k x k windows with zero padding counted in the divisor k*k.
+torch::Tensor avgpool_fwd(torch::Tensor x, int64_t k, int64_t stride,
+                          int64_t pad) {
+  check_avgpool_operand(x, "x");
+  check_avgpool_window(k, stride, pad);
+  const int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  check_conv_geometry("avgpool", N, H, W, k, k, stride, pad);
+  auto y = empty_nhwc(x, N, C, conv_out_size(H, pad, k, stride),
+                      conv_out_size(W, pad, k, stride));
+  launch_avgpool_fwd(x.data_ptr(), y.data_ptr(), N, C, H, W, (int)k,
+                     (int)stride, (int)pad, cur_stream());
+  return y;
+}
+
+// dy: (N,C,OH,OW) channels_last of the pool of an (N,C,H,W) input. Returns
+// channels_last dx, fully written.
+torch::Tensor avgpool_bwd(torch::Tensor dy, int64_t H, int64_t W, int64_t k,
+                          int64_t stride, int64_t pad) {
+  check_avgpool_operand(dy, "dy");
+  check_avgpool_window(k, stride, pad);
+  const int64_t N = dy.size(0), C = dy.size(1);
+  TORCH_CHECK(H < (1 << 15) && W < (1 << 15) &&
+                  N * C * H * W < (int64_t(1) << 40),
+              "avgpool: tensor too large");
+  check_conv_geometry("avgpool", N, H, W, k, k, stride, pad);
+  check_conv_dy("avgpool", dy, N, H, W, k, k, stride, pad);
+  auto dx = empty_nhwc(dy, N, C, H, W);
+  launch_avgpool_bwd(dy.data_ptr(), dx.data_ptr(), (int)N, (int)C, (int)H,
+                     (int)W, (int)k, (int)stride, (int)pad, cur_stream());
+  return dx;
+}
+
+// x: (N,C,H,W) channels_last -> (N,C,1,1), the mean over H x W.
+torch::Tensor global_avgpool_fwd(torch::Tensor x) {
+  check_avgpool_operand(x, "x");
+  const int64_t N = x.size(0), C = x.size(1);
+  const int64_t HW = x.size(2) * x.size(3);
+  auto y = empty_nhwc(x, N, C, 1, 1);
+  launch_global_avgpool_fwd(x.data_ptr(), y.data_ptr(), N, (int)C, (int)HW,
+                            cur_stream());
+  return y;
+}
+
+// dy: (N,C,1,1). Returns channels_last dx (N,C,H,W) = dy / (H*W).
+torch::Tensor global_avgpool_bwd(torch::Tensor dy, int64_t H, int64_t W) {
+  check_avgpool_operand(dy, "dy");
+  TORCH_CHECK(dy.size(2) == 1 && dy.size(3) == 1,
+              "avgpool: dy of a global pool must be (N, C, 1, 1)");
+  const int64_t N = dy.size(0), C = dy.size(1);
+  TORCH_CHECK(H >= 1 && W >= 1 && H < (1 << 15) && W < (1 << 15) &&
+                  N * C * H * W < (int64_t(1) << 40),
+              "avgpool: bad input size");
+  auto dx = empty_nhwc(dy, N, C, H, W);
+  launch_global_avgpool_bwd(dy.data_ptr(), dx.data_ptr(), N, (int)C,
+                            (int)(H * W), cur_stream());
+  return dx;
+}
+
+// Host decisions for an (N,C,H,W) input: "global" is the global pool's
+// plan; with a window (k > 0), "fwd" and "bwd" are the windowed tilings.
+py::dict avgpool_plan_py(int64_t N, int64_t C, int64_t H, int64_t W,
+                         int64_t k, int64_t stride, int64_t pad) {
+  py::dict d;
+  const GapPlan g = global_avgpool_plan(N, (int)C, (int)(H * W));
+  py::dict gd;
+  gd["V"] = g.V;
+  gd["split"] = (bool)g.split;
+  gd["cvb"] = g.cvb;
+  gd["psplit"] = g.psplit;
+  gd["fwd_blocks"] = g.fwd_blocks;
+  gd["bwd_blocks"] = g.bwd_blocks;
+  d["global"] = gd;
+  if (k > 0) {
+    check_avgpool_window(k, stride, pad);
+    check_conv_geometry("avgpool", N, H, W, k, k, stride, pad);
+    auto tiling = [](const AvgWinPlan& t) {
+      py::dict w;
+      w["V"] = t.V;
+      w["tile"] = py::make_tuple(t.th, t.tw, t.cvb);
+      w["grid"] = py::make_tuple(t.tiles_h, t.tiles_w, t.nct);
+      w["tiles"] = t.tiles;
+      w["blocks"] = t.blocks;
+      return w;
+    };
+    d["fwd"] = tiling(avgpool_win_plan((int)N, (int)C,
+                                       conv_out_size(H, pad, k, stride),
+                                       conv_out_size(W, pad, k, stride)));
+    d["bwd"] = tiling(avgpool_win_plan((int)N, (int)C, (int)H, (int)W));
+  }
+  return d;
+}
+
 // ---- depthwise 3x3 ----------------------------------------------------
 torch::Tensor dw3x3_fwd(torch::Tensor x, torch::Tensor w, int64_t stride,
                         bool nhwc) {
@@ -1552,6 +1671,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("masked"));
   m.def("maxpool_fwd", &maxpool_fwd, "NHWC bf16 max-pool forward");
   m.def("maxpool_bwd", &maxpool_bwd, "NHWC bf16 max-pool backward");
+  m.def("avgpool_fwd", &avgpool_fwd,
+        "NHWC bf16 average pool forward, (k,stride,pad) in "
+        "{(3,1,1),(3,2,1),(2,2,0)}",
+        py::arg("x"), py::arg("k"), py::arg("stride"), py::arg("pad"));
+  m.def("avgpool_bwd", &avgpool_bwd, "NHWC bf16 average pool backward",
+        py::arg("dy"), py::arg("H"), py::arg("W"), py::arg("k"),
+        py::arg("stride"), py::arg("pad"));
+  m.def("global_avgpool_fwd", &global_avgpool_fwd,
+        "NHWC bf16 global average pool forward -> (N,C,1,1)");
+  m.def("global_avgpool_bwd", &global_avgpool_bwd,
+        "NHWC bf16 global average pool backward", py::arg("dy"),
+        py::arg("H"), py::arg("W"));
+  m.def("avgpool_plan", &avgpool_plan_py,
+        "host decisions of the average pool launchers for a shape",
+        py::arg("N"), py::arg("C"), py::arg("H"), py::arg("W"),
+        py::arg("k") = 0, py::arg("stride") = 0, py::arg("pad") = 0);
   m.def("conv_igemm_fwd", &conv_igemm_fwd,
         "NHWC bf16 MFMA implicit-GEMM conv forward");
   m.def("conv_igemm_dgrad", &conv_igemm_dgrad,

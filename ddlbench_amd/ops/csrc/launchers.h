@@ -330,6 +330,40 @@ void launch_maxpool_bwd(const void*, const unsigned char*, void*,
                         int64_t, int64_t, int, int, int, int, int, int,
                         int, hipStream_t);
 
+// ---- avgpool.hip: bf16 NHWC average pooling, C % 4 == 0 (throws
+// otherwise); channel vectors of V = 8 when C % 8 == 0, else of 4 ---------
+// Tiling of a windowed kernel over the tensor it writes (WH x WW per image):
+// a tile is th rows x tw columns x cvb channel vectors, `blocks` blocks walk
+// `tiles` tiles grid-stride. Pure host code.
+struct AvgWinPlan {
+  int V, cvb, nct;
+  int tw, th, tiles_w, tiles_h;
+  long tiles;
+  int blocks;
+};
+AvgWinPlan avgpool_win_plan(int N, int C, int WH, int WW);
+// (k, stride, pad) in {(3,1,1), (3,2,1), (2,2,0)} (throws otherwise),
+// count_include_pad, no ceil_mode. N, C, H, W are x's in both.
+void launch_avgpool_fwd(const void* x, void* y, int N, int C, int H, int W,
+                        int k, int stride, int pad, hipStream_t stream);
+// dx is fully written
+void launch_avgpool_bwd(const void* dy, void* dx, int N, int C, int H, int W,
+                        int k, int stride, int pad, hipStream_t stream);
+// Global pool over HW pixels. split = 1: the forward splits the pixel axis
+// over psplit threads per channel vector, cvb channel vectors per block;
+// 0: one thread per (image, channel vector).
+struct GapPlan {
+  int V, split, cvb, nct, psplit;
+  int fwd_blocks, bwd_blocks;
+};
+GapPlan global_avgpool_plan(long N, int C, int HW);
+// x: (N, HW, C) memory -> y: (N, C)
+void launch_global_avgpool_fwd(const void* x, void* y, long N, int C, int HW,
+                               hipStream_t stream);
+// dx[n, px, c] = dy[n, c] / HW
+void launch_global_avgpool_bwd(const void* dy, void* dx, long N, int C,
+                               int HW, hipStream_t stream);
+
 // ---- seq_utils.hip ----------------------------------------------------
 template <typename T>
 void launch_revert_varlen(const T*, T*, const int64_t*, int64_t, int64_t,

@@ -25,6 +25,7 @@ CSRC = ROOT / "ddlbench_amd" / "ops" / "csrc"
 KERNEL_SOURCES = [
     "attn_ctx.hip",
     "attn_score.hip",
+    "avgpool.hip",
     "bindings.hip",
     "bn_act.hip",
     "conv_depthwise.hip",
