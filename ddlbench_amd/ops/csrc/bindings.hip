@@ -112,6 +112,36 @@ bool bn_layout_ok(const torch::Tensor& t, bool nhwc) {
               : t.is_contiguous();
 }
 
+// A full-size operand of the BN+act bindings (res, y, dy) against x: the
+// kernels index it exactly as they index x, so a tensor of another size,
+// dtype, device or layout would be reinterpreted silently.
+void check_bn_like_x(const torch::Tensor& t, const char* name,
+                     const torch::Tensor& x, bool nhwc) {
+  TORCH_CHECK(t.sizes() == x.sizes(), name, " and x differ in size");
+  TORCH_CHECK(t.scalar_type() == x.scalar_type(), name,
+              " and x differ in dtype");
+  TORCH_CHECK(t.device() == x.device(), name, " and x differ in device");
+  TORCH_CHECK(bn_layout_ok(t, nhwc), name, " layout mismatch");
+}
+
+// A per-channel operand (gamma, beta, statistics): the kernels read and
+// write it as C consecutive floats.
+void check_bn_channel_vec(const torch::Tensor& t, const char* name,
+                          const torch::Tensor& x) {
+  TORCH_CHECK(t.device() == x.device() && t.scalar_type() == at::kFloat &&
+                  t.is_contiguous() && t.numel() == x.size(1),
+              name, " must be a contiguous fp32 tensor of C elements on "
+              "x's device");
+}
+
+void check_bn_x(const torch::Tensor& x, bool nhwc) {
+  TORCH_CHECK(x.is_cuda(), "x must be on the HIP device");
+  TORCH_CHECK(x.dim() == 4, "x must be 4-D");
+  TORCH_CHECK(is_bf16(x) || x.scalar_type() == at::kFloat,
+              "x must be bf16 or fp32");
+  TORCH_CHECK(bn_layout_ok(x, nhwc), "x layout mismatch");
+}
+
 // is_cuda + bf16 + channels_last, the operand contract of the conv and
 // pool bindings; `op` prefixes the dtype message
 void check_conv_operand(const torch::Tensor& t, const char* name,
@@ -195,9 +225,14 @@ std::vector<torch::Tensor> bn_act_fwd(
     torch::Tensor beta, c10::optional<torch::Tensor> running_mean,
     c10::optional<torch::Tensor> running_var, bool training, double momentum,
     double eps, int64_t act, bool nhwc) {
-  TORCH_CHECK(x.is_cuda(), "x must be on the HIP device");
-  TORCH_CHECK(x.dim() == 4, "x must be 4-D");
-  TORCH_CHECK(bn_layout_ok(x, nhwc), "x layout mismatch");
+  check_bn_x(x, nhwc);
+  if (res) check_bn_like_x(*res, "res", x, nhwc);
+  check_bn_channel_vec(gamma, "gamma", x);
+  check_bn_channel_vec(beta, "beta", x);
+  if (running_mean) check_bn_channel_vec(*running_mean, "running_mean", x);
+  if (running_var) check_bn_channel_vec(*running_var, "running_var", x);
+  TORCH_CHECK(running_mean.has_value() == running_var.has_value(),
+              "running_mean and running_var come together");
   const int64_t N = x.size(0), C = x.size(1), HW = x.size(2) * x.size(3);
   const BnPlan plan = bn_plan(N, C, HW, nhwc, (int)x.element_size(),
                               (int)act, training, /*masked=*/0);
@@ -256,7 +291,7 @@ std::vector<torch::Tensor> bn_act_bwd(torch::Tensor dy,
                                       bool nhwc,
                                       c10::optional<torch::Tensor> msk,
                                       c10::optional<torch::Tensor> gate) {
-  TORCH_CHECK(dy.is_cuda(), "dy must be on the HIP device");
+  check_bn_x(x, nhwc);
   if (gate) {
     TORCH_CHECK(act == 0 && !msk && !need_dres,
                 "bn_act_bwd: a foreign gate is for an act == 0 layer with "
@@ -274,10 +309,11 @@ std::vector<torch::Tensor> bn_act_bwd(torch::Tensor dy,
   }
   TORCH_CHECK(y_opt || msk,
               "bn_act_bwd needs y or the 1-bit activation mask");
-  TORCH_CHECK(dy.sizes() == x.sizes(), "dy and x differ in size");
-  TORCH_CHECK(dy.scalar_type() == x.scalar_type(),
-              "dy and x differ in dtype");
-  TORCH_CHECK(bn_layout_ok(dy, nhwc), "dy layout mismatch");
+  check_bn_like_x(dy, "dy", x, nhwc);
+  if (y_opt) check_bn_like_x(*y_opt, "y", x, nhwc);
+  check_bn_channel_vec(mean, "mean", x);
+  check_bn_channel_vec(invstd, "invstd", x);
+  check_bn_channel_vec(gamma, "gamma", x);
   const int64_t N = x.size(0), C = x.size(1), HW = x.size(2) * x.size(3);
   TORCH_CHECK(!msk || msk->numel() == x.numel() / 8,
               "the activation mask must hold numel/8 bytes");

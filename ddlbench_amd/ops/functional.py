@@ -112,7 +112,9 @@ class _FusedBNAct(torch.autograd.Function):
         ext = _ops.require_extension()
         nhwc = _is_nhwc(x)
         x = _layout_contiguous(x, nhwc)
-        res = _layout_contiguous(res, nhwc) if res is not None else None
+        if res is not None:
+            # the kernels read res as they read x: same dtype, same layout
+            res = _layout_contiguous(res.to(x.dtype), nhwc)
         outs = ext.bn_act_fwd(x, res, gamma, beta, running_mean,
                               running_var, training, momentum,
                               eps, act_code, nhwc)
@@ -181,7 +183,8 @@ def bn_act(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
     is the block's GateSlot: with ``res`` this BN produces the gated
     shortcut gradient, without it (``act="none"``) it consumes one."""
     if _ops.use_native(x, backend):
-        return _FusedBNAct.apply(x, gamma.float(), beta.float(), res,
+        return _FusedBNAct.apply(x, gamma.float().contiguous(),
+                                 beta.float().contiguous(), res,
                                  running_mean, running_var, training,
                                  momentum, eps, _ACT[act], gate)
     y = F.batch_norm(x, running_mean, running_var, gamma, beta, training,

@@ -11,6 +11,11 @@ fails those assertions.
 Every case also runs with act = none on integer inputs (the exactness
 test), so the act-none plan of its shape counts towards its tags.
 
+Two data sets per case: ``case_inputs`` (seeded normal data, compared with
+float64 at a tolerance) and ``dyadic_inputs`` (data on which the whole
+computation is exact in fp32 and bf16 in any summation order, compared bit
+for bit; tests/test_bn_cases_cpu.py proves that property on the CPU).
+
 The shapes are the smallest that reach each path:
   rows = N*H*W >= 32768 switches apply/dx to the fixed-channel kernels
   (as does a mask to write or read); C <= 512 with C % 8 == 0 selects the
@@ -113,13 +118,55 @@ CASES = [
          ("mask",), ("S=2048", "fin:Y=64", "fin:f32")),
     Case("fin_s128_c512", BF, True, (8, 512, 16, 16), "relu", False, True,
          ("mask",), ("S=128", "fin:Y>1", "stats:nhwc_vec:bf16")),
+    # edge geometries
+    # rows = 1615, S = 100, 17 rows per slice: slices 95..99 start past the
+    # last row in the reduce, the fixed-channel apply and its dx
+    Case("empty_slices", BF, True, (5, 8, 17, 19), "relu", False, True,
+         ("mask", "y"),
+         ("slices:empty", "S=100", "rows:odd", "apply:fixed_channel:mask",
+          "dx:fixed_channel:mask")),
+    # one row: var = 0, the unbiased guard
+    Case("count1_nhwc_bf16", BF, True, (1, 8, 1, 1), "relu", False, True,
+         ("mask", "y"), ("count=1", "stats:nhwc_vec:bf16")),
+    Case("count1_nchw_bf16", BF, False, (1, 8, 1, 1), "relu", False, True,
+         ("y",), ("count=1", "stats:nchw:bf16")),
+    Case("count1_nhwc_fp32", FP, True, (1, 8, 1, 1), "relu", False, True,
+         ("y",), ("count=1", "stats:nhwc_scalar:fp32")),
+    Case("count1_nchw_fp32", FP, False, (1, 8, 1, 1), "relu", False, True,
+         ("y",), ("count=1", "stats:nchw:fp32")),
+    # 3 rows against 128 row-groups
+    Case("rows3_c16", BF, True, (1, 16, 1, 3), "relu", False, True,
+         ("mask", "y"), ("rows<RG", "stats:nhwc_vec:bf16")),
+    # C % 8 == 0 but > 512: scalar reduce reading the mask; 65 lanes = two
+    # lane blocks of the fixed-channel grid, the second with one live lane
+    Case("c520_relu", BF, True, (2, 520, 3, 3), "relu", False, True,
+         ("mask", "y"),
+         ("fixed:tail_lane_block", "fixed:lane_blocks=2",
+          "bwd_reduce:nhwc_scalar:bf16:mask", "dx:fixed_channel:mask")),
+    Case("c4_bf16", BF, True, (2, 4, 3, 3), "relu", False, True,
+         ("y",), ("C<8", "apply:scalar:nhwc:bf16", "dx:scalar:nhwc:bf16")),
+    Case("c4_fp32", FP, True, (2, 4, 3, 3), "relu", False, True,
+         ("y",), ("C<8", "apply:scalar:nhwc:fp32", "dx:scalar:nhwc:fp32")),
+    # HW = 1: every element its own (n, c)
+    Case("nchw_hw1", BF, False, (16, 8, 1, 1), "relu", False, True,
+         ("y",), ("nchw:hw1", "apply:scalar:nchw:bf16")),
+    # eval beyond the small NHWC vec kernels: fixed-channel apply with an
+    # act and no mask, fixed-channel dx with k2 = k3 = 0; NCHW vec, scalar
+    Case("rows32k_relu_eval", BF, True, (8, 8, 64, 64), "relu", False, False,
+         ("y",), ("eval:fixed_channel", "apply:fixed_channel:nomask",
+                  "apply:fixed_channel:act1", "dx:fixed_channel:y")),
+    Case("nchw_fp32_hw64_relu6_eval", FP, False, (4, 16, 8, 8), "relu6",
+         False, False, ("y",), ("eval:nchw", "eval:nchw:vec")),
+    Case("nchw_bf16_hw196_eval", BF, False, (8, 32, 14, 14), "relu", False,
+         False, ("y",), ("eval:nchw", "eval:nchw:scalar")),
 ]
 
 CASE_BY_NAME = {c.name: c for c in CASES}
 assert len(CASE_BY_NAME) == len(CASES)
 
 # cases of the masked-vs-unmasked bit-for-bit cross-check (relu only)
-CROSS_CHECK = ("c8_relu_train", "rows32k_relu", "c1024_relu", "c24_relu_res")
+CROSS_CHECK = ("c8_relu_train", "rows32k_relu", "c1024_relu", "c24_relu_res",
+               "empty_slices", "c520_relu")
 
 _REDUCES = [("nchw", "bf16"), ("nchw", "fp32"), ("nhwc_scalar", "bf16"),
             ("nhwc_scalar", "fp32"), ("nhwc_vec", "bf16")]
@@ -127,6 +174,9 @@ _ELTS = [("fixed_channel", "nhwc", "bf16")] + [
     (k, lay, d) for k in ("vec", "scalar") for lay in ("nhwc", "nchw")
     for d in ("bf16", "fp32")]
 _KINDS = ("fixed_channel", "vec", "scalar")
+# block geometry of the NHWC kernels (bn_act.hip): threads per block and
+# the most channel lanes a block holds
+BLOCK, LANES = 256, 64
 
 REQUIRED = sorted(set(
     [f"stats:{k}:{d}" for k, d in _REDUCES]
@@ -147,7 +197,10 @@ REQUIRED = sorted(set(
        "dx:fixed_channel:mask:act2"]
     + ["fin:f32", "fin:f64", "fin:Y=1", "fin:Y>1", "fin:Y=64",
        "cblocks=16", "fixed:lane_blocks=2", "rows:odd"]
-    + [f"S={s}" for s in (2, 128, 2048)]))
+    + ["slices:empty", "count=1", "rows<RG", "fixed:tail_lane_block", "C<8",
+       "nchw:hw1", "eval:fixed_channel", "eval:nchw", "eval:nchw:vec",
+       "eval:nchw:scalar"]
+    + [f"S={s}" for s in (2, 100, 128, 2048)]))
 
 
 def dtype_name(dtype):
@@ -203,8 +256,31 @@ def _tags_of(ext, case, act, add, training, gates):
             tags.add(f"bwd_reduce:{red}:mask:act{act}")
         if dg == "mask":
             tags |= {f"dx:{dx}:mask:act{act}", f"dx:{dx}:mask:{r}"}
-    if (N * H * W) % 2:
+        # edge geometries, from the plan and the kernels' own slicing
+        rows, S = N * H * W, pl["S"]
+        if (S - 1) * -(-rows // S) >= rows:
+            tags.add("slices:empty")
+        if case.nhwc:
+            lanes = C // 8 if red == "nhwc_vec" else C
+            if rows < BLOCK // min(lanes, LANES):
+                tags.add("rows<RG")
+        if ap == "fixed_channel" and pl["apply_grid"][0] > 1 \
+                and (C // 8) % LANES == 1:
+            tags.add("fixed:tail_lane_block")
+        if not training:
+            if ap == "fixed_channel" and dx == "fixed_channel" and act != 0:
+                tags.add("eval:fixed_channel")
+            if not case.nhwc:
+                tags |= {"eval:nchw", f"eval:nchw:{ap}"}
+    rows = N * H * W
+    if rows % 2:
         tags.add("rows:odd")
+    if rows == 1:
+        tags.add("count=1")
+    if C < 8 and case.nhwc:
+        tags.add("C<8")
+    if not case.nhwc and H * W == 1 and N > 1:
+        tags.add("nchw:hw1")
     return tags
 
 
@@ -264,56 +340,191 @@ def integer_inputs(shape, dtype, nhwc):
     return _layout(x, nhwc), _layout(dy, nhwc)
 
 
-@functools.lru_cache(maxsize=None)
-def reference64(name):
-    """float64 BN (+res) + act and its autograd on the CPU, from the
-    case's own inputs."""
+# ---------------------------------------------------------- dyadic data
+# Data on which BN+act is exact in fp32 and bf16 whatever the summation
+# order or fma contraction. With R = N*H*W rows and P = R // 4, channel c
+# holds x = m_c + d: m_c an integer in -3..3, d = +2 at P seeded rows, -2
+# at P others, 0 elsewhere. So sum x = R*m_c, sum x^2 = R*m_c^2 + 8P, the
+# mean is m_c and the biased variance 8P/R; eps = float32(4 - 8P/R) makes
+# var + eps = 4 to within 2^-25 and invstd exactly 0.5, hence xhat in
+# {-1, 0, 1}. gamma in {0.5, 1, 2, -1} (and 4 for relu6, so that the upper
+# clamp is reached), beta an odd multiple of 0.25 below 3 in magnitude, res
+# in {-1, -0.5, 0, 0.5, 1}: v = gamma*xhat + beta (+res) is an odd multiple
+# of 0.25, never 0 or 6, and y is bf16-exact. dy is an integer in -2..2, so
+# dgamma and dbeta are integers. Eval cases take running_mean = m_c,
+# running_var = 2 and eps = 2 for the same invstd.
+DY_MOM = 0.5
+_GAMMAS = (0.5, 1.0, 2.0, -1.0)
+
+
+def _pick(values, n, g):
+    v = torch.tensor(values, dtype=torch.float64)
+    return v[torch.randint(len(values), (n,), generator=g)]
+
+
+def dyadic64(name):
+    """The dyadic data of one case in float64, NCHW-contiguous, before the
+    cast to the case's dtype (which test_bn_cases_cpu.py proves lossless)."""
     case = CASE_BY_NAME[name]
-    d = case_inputs(name)
-    x = d["x"].double().contiguous().requires_grad_(True)
-    res = d["res"].double().contiguous().requires_grad_(True) \
-        if case.res else None
-    gamma = d["gamma"].double().requires_grad_(True)
-    beta = d["beta"].double().requires_grad_(True)
-    rm, rv = d["rm"].double().clone(), d["rv"].double().clone()
-    v = F.batch_norm(x, rm, rv, gamma, beta, case.training, MOM, EPS)
+    N, C, H, W = case.shape
+    R = N * H * W
+    P = R // 4
+    g = torch.Generator().manual_seed(5200 + CASES.index(case))
+    m = torch.randint(-3, 4, (C,), generator=g).double()
+    perm = torch.rand(C, R, generator=g).argsort(dim=1)
+    dev = torch.zeros(C, R, dtype=torch.float64)
+    dev.scatter_(1, perm[:, :P], 2.0)
+    dev.scatter_(1, perm[:, P:2 * P], -2.0)
+    x = (m.view(C, 1) + dev).view(C, N, H, W).permute(1, 0, 2, 3).contiguous()
+    gamma = _pick(_GAMMAS + ((4.0,) if case.act == "relu6" else ()), C, g)
+    beta = (2 * torch.randint(-6, 6, (C,), generator=g).double() + 1) / 4
+    gamma[C - 1] = -1.0
+    if case.act == "relu6":
+        gamma[0], beta[0] = 4.0, 2.75      # v = 6.75 where xhat = 1
+    d = {"x": x, "m": m, "P": P, "R": R, "gamma": gamma, "beta": beta,
+         "dy": torch.randint(-2, 3, case.shape, generator=g).double(),
+         "res": torch.randint(-2, 3, case.shape, generator=g).double() / 2
+         if case.res else None}
+    if case.training:
+        d["rm"] = 2 * torch.randint(-2, 3, (C,), generator=g).double()
+        d["rv"] = torch.zeros(C, dtype=torch.float64)
+        d["eps"] = float(torch.tensor(4.0 - 8.0 * P / R,
+                                      dtype=torch.float32))
+    else:
+        d["rm"], d["rv"], d["eps"] = m.clone(), torch.full_like(m, 2.0), 2.0
+    return d
+
+
+@functools.lru_cache(maxsize=None)
+def dyadic_inputs(name):
+    """dyadic64 in the case's dtype and layout (gamma, beta and the running
+    statistics in fp32); shared read-only between the tests."""
+    case = CASE_BY_NAME[name]
+    d = dyadic64(name)
+    for k in ("x", "dy", "res"):
+        if d[k] is not None:
+            d[k] = _layout(d[k].to(case.dtype), case.nhwc)
+    for k in ("gamma", "beta", "rm", "rv"):
+        d[k] = d[k].float()
+    return d
+
+
+def formulas64(case, d, mean, invstd, gate=None):
+    """The kernels' documented formulas in float64, from inputs ``d`` (a
+    case_inputs / dyadic_inputs dict) and per-channel mean and invstd:
+      v = gamma*xhat + beta (+res), y = act(v), g = dy*gate,
+      dbeta = sum g, dgamma = sum g*xhat, dres = g,
+      dx = k1*(g - k2 - xhat*k3), k1 = gamma*invstd, k2 = dbeta/R and
+      k3 = dgamma/R (both 0 in eval mode).
+    gate: the 0/1 activation gate to use (the kernel's own); default the
+    reference's, v > 0 for relu and 0 < v < 6 for relu6."""
+    N, C, H, W = case.shape
+    R = N * H * W
+
+    def ch(t):
+        return t.double().view(1, C, 1, 1)
+    x, dy = d["x"].double().contiguous(), d["dy"].double().contiguous()
+    xhat = (x - ch(mean)) * ch(invstd)
+    v = ch(d["gamma"]) * xhat + ch(d["beta"])
     if case.res:
-        v = v + res
+        v = v + d["res"].double().contiguous()
     y = {"none": v, "relu": torch.relu(v),
          "relu6": torch.clamp(v, 0, 6)}[case.act]
-    y.backward(d["dy"].double().contiguous())
+    own = {"none": torch.ones_like(v, dtype=torch.bool), "relu": v > 0,
+           "relu6": (v > 0) & (v < 6)}[case.act]
+    g = dy * (own if gate is None else gate).double()
+    dbeta = g.sum(dim=(0, 2, 3))
+    dgamma = (g * xhat).sum(dim=(0, 2, 3))
+    k1 = d["gamma"].double() * invstd.double()
+    k2 = dbeta / R if case.training else torch.zeros_like(dbeta)
+    k3 = dgamma / R if case.training else torch.zeros_like(dgamma)
+    dx = ch(k1) * (g - ch(k2) - xhat * ch(k3))
+    return {"xhat": xhat, "v": v, "y": y, "gate": own, "g": g,
+            "dbeta": dbeta, "dgamma": dgamma, "k1": k1, "k2": k2, "k3": k3,
+            "dx": dx, "dres": g}
+
+
+def unpack_mask(mask, case):
+    """The forward's 1-bit mask as a bool tensor of the case's (N, C, H, W):
+    bit i & 7 of byte i / 8, i the element's index in NHWC memory order."""
     N, C, H, W = case.shape
+    assert case.nhwc and mask.dtype is torch.uint8 and mask.dim() == 1
+    bits = (mask.cpu().to(torch.int32).view(-1, 1)
+            >> torch.arange(8, dtype=torch.int32)) & 1
+    return bits.view(N, H, W, C).permute(0, 3, 1, 2).bool()
+
+
+def kernel_gate(case, r, gate):
+    """The gate one backward run of ``r`` (a run_case result) used: the
+    unpacked mask, or the activation's gate on the returned y."""
+    if case.act == "none":
+        return torch.ones(case.shape, dtype=torch.bool)
+    if gate == "mask":
+        return unpack_mask(r["mask"], case)
+    y = r["y"].cpu().double().contiguous()
+    return (y > 0) & (y < 6) if case.act == "relu6" else y > 0
+
+
+def within_one_ulp(got, ref):
+    """got equals ref or one of its two neighbours in ref's dtype."""
+    up = torch.nextafter(ref, torch.full_like(ref, float("inf")))
+    dn = torch.nextafter(ref, torch.full_like(ref, float("-inf")))
+    return bool(((got == ref) | (got == up) | (got == dn)).all())
+
+
+def half_ulp_bf16(ref64):
+    """Half a bf16 ulp (8 significant bits) at each element of ref64."""
+    _, e = torch.frexp(ref64.abs())          # |ref| = mant * 2^e, mant < 1
+    h = torch.ldexp(torch.ones_like(ref64), e - 9)
+    return torch.where(ref64 == 0, torch.zeros_like(ref64), h)
+
+
+@functools.lru_cache(maxsize=None)
+def reference64(name):
+    """float64 BN (+res) + act on the CPU from the case's own inputs, and
+    the float64 statistics the backward reference (formulas64, with the
+    kernel's own gate) is built from. One row per channel, which
+    F.batch_norm refuses in training mode, takes the formulas with var = 0
+    and the kernel's unbiased guard (running_var moves towards 0)."""
+    case = CASE_BY_NAME[name]
+    d = case_inputs(name)
+    N, C, H, W = case.shape
+    x = d["x"].double().contiguous()
+    rm, rv = d["rm"].double().clone(), d["rv"].double().clone()
     if case.training:
-        mean = d["x"].double().mean(dim=(0, 2, 3))
-        var = d["x"].double().var(dim=(0, 2, 3), unbiased=False)
+        mean = x.mean(dim=(0, 2, 3))
+        var = x.var(dim=(0, 2, 3), unbiased=False)
     else:
-        mean, var = d["rm"].double(), d["rv"].double()
-    xhat = (d["x"].double() - mean.view(1, C, 1, 1)) \
-        * torch.rsqrt(var + EPS).view(1, C, 1, 1)
-    return {"y": y.detach(), "rm": rm, "rv": rv, "mean": mean,
-            "invstd": torch.rsqrt(var + EPS), "xhat": xhat,
-            "dx": x.grad, "dgamma": gamma.grad, "dbeta": beta.grad,
-            "dres": res.grad if case.res else None}
+        mean, var = rm.clone(), rv.clone()
+    invstd = torch.rsqrt(var + EPS)
+    if case.training and N * H * W == 1:
+        y = formulas64(case, d, mean, invstd)["y"]
+        rm = (1 - MOM) * rm + MOM * mean
+        rv = (1 - MOM) * rv + MOM * var
+    else:
+        v = F.batch_norm(x, rm, rv, d["gamma"].double(), d["beta"].double(),
+                         case.training, MOM, EPS)
+        if case.res:
+            v = v + d["res"].double().contiguous()
+        y = {"none": v, "relu": torch.relu(v),
+             "relu6": torch.clamp(v, 0, 6)}[case.act]
+    return {"y": y, "rm": rm, "rv": rv, "mean": mean, "invstd": invstd}
 
 
 # ------------------------------------------------------------------- run
-def run_case(ext, case, dev):
-    """The case through ext.bn_act_fwd and one ext.bn_act_bwd per gate
-    source in case.bwd. Returns a flat dict of device tensors (bwd results
-    keyed '<name>@<gate>'); uses nothing but the two bindings."""
-    d = case_inputs(case.name)
+def _run(ext, case, d, dev, mom, eps, gates):
     x, dy = d["x"].to(dev), d["dy"].to(dev)
     res = d["res"].to(dev) if case.res else None
     gamma, beta = d["gamma"].to(dev), d["beta"].to(dev)
     rm, rv = d["rm"].to(dev), d["rv"].to(dev)
     act = ACT[case.act]
-    outs = ext.bn_act_fwd(x, res, gamma, beta, rm, rv, case.training, MOM,
-                          EPS, act, case.nhwc)
+    outs = ext.bn_act_fwd(x, res, gamma, beta, rm, rv, case.training, mom,
+                          eps, act, case.nhwc)
     out = {"y": outs[0], "mean": outs[1], "invstd": outs[2], "rm": rm,
            "rv": rv}
     if len(outs) > 3:
         out["mask"] = outs[3]
-    for gate in case.bwd:
+    for gate in gates:
         if gate == "mask":
             assert "mask" in out, f"{case.name}: forward wrote no mask"
             y_arg, m_arg = None, out["mask"]
@@ -324,3 +535,22 @@ def run_case(ext, case, dev):
         for k, t in zip(("dx", "dgamma", "dbeta", "dres"), b):
             out[f"{k}@{gate}"] = t
     return out
+
+
+def run_case(ext, case, dev):
+    """The case through ext.bn_act_fwd and one ext.bn_act_bwd per gate
+    source in case.bwd. Returns a flat dict of device tensors (bwd results
+    keyed '<name>@<gate>'); uses nothing but the two bindings."""
+    return _run(ext, case, case_inputs(case.name), dev, MOM, EPS, case.bwd)
+
+
+def dyadic_gates(case):
+    """Both gate sources wherever the forward writes a mask."""
+    return ("mask", "y") if writes_mask(case) else ("y",)
+
+
+def run_dyadic(ext, case, dev):
+    """run_case on the dyadic data, backward from every gate source."""
+    d = dyadic_inputs(case.name)
+    return _run(ext, case, d, dev, DY_MOM, d["eps"], dyadic_gates(case))
+

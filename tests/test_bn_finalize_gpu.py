@@ -21,6 +21,8 @@ for the running statistics); two calls must agree bit for bit."""
 import pytest
 import torch
 
+from bn_cases import within_one_ulp
+
 pytestmark = pytest.mark.gpu
 
 EPS = 1e-5
@@ -97,10 +99,7 @@ def _running(prev, new32):
     return (1 - mom) * prev + mom * new32
 
 
-def _within_one_ulp(got, ref):
-    up = torch.nextafter(ref, torch.full_like(ref, float("inf")))
-    dn = torch.nextafter(ref, torch.full_like(ref, float("-inf")))
-    return bool(((got == ref) | (got == up) | (got == dn)).all())
+_within_one_ulp = within_one_ulp
 
 
 # --------------------------------------------------------------- exact
@@ -186,9 +185,12 @@ def test_random_inputs_and_determinism(ext, case, with_res):
 def test_back_to_back_layers_share_workspace(ext):
     """Large C*S, then a small layer, then another large one on the same
     stream with no sync in between: the slab workspace, the second-level
-    partials and the ticket words are reused call after call."""
+    partials and the ticket words are reused call after call. The 1615-row
+    layer in between (S = 100 slices of 17 rows, the last five empty, Y = 4)
+    writes zero slabs for its empty slices over the large layer's sums and
+    draws tickets on the word the large layers use."""
     shapes = [(8, 64, 64, 64), (2, 8, 4, 4), (8, 512, 16, 16),
-              (4, 1024, 8, 8), (8, 64, 64, 64)]
+              (5, 8, 17, 19), (4, 1024, 8, 8), (8, 64, 64, 64)]
     runs = [_run_random(ext, s, torch.bfloat16, False, seed=20 + i)
             for i, s in enumerate(shapes)]
     torch.cuda.synchronize()
