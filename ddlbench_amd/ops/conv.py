@@ -517,7 +517,8 @@ class Conv2dLine(_NativeConv2d):
 
 def convert_convs(model: nn.Module, dtype=torch.bfloat16,
                   stem=None, grouped=None, depthwise="library",
-                  line="library", avgpool="library") -> int:
+                  line="library", avgpool="library",
+                  linear="library") -> int:
     """Replace eligible nn.Conv2d children with Conv2dMFMA and eligible
     nn.MaxPool2d with the native NHWC pool. Returns the number of
     conversions.
@@ -531,12 +532,15 @@ def convert_convs(model: nn.Module, dtype=torch.bfloat16,
     variable and defaults to "library". ``line="native"`` does the same
     for line_eligible (1,T) / (T,1) convs (Conv2dLine), and
     ``avgpool="native"`` for avgpool_eligible nn.AvgPool2d /
-    nn.AdaptiveAvgPool2d(1) children (ops.pool.convert_avgpools)."""
+    nn.AdaptiveAvgPool2d(1) children (ops.pool.convert_avgpools), and
+    ``linear="native"`` for linear_eligible nn.Linear children
+    (ops.modules.convert_linears)."""
     stem = resolve("stem", stem)
     grouped = resolve("grouped", grouped)
     check("depthwise", depthwise, ("native", "library"))
     check("line", line, ("native", "library"))
     check("avgpool", avgpool, ("native", "library"))
+    check("linear", linear, ("native", "library"))
     count = 0
     for parent in model.modules():
         for name, child in list(parent.named_children()):
@@ -563,4 +567,7 @@ def convert_convs(model: nn.Module, dtype=torch.bfloat16,
     if dtype == torch.bfloat16 and avgpool == "native":
         from ddlbench_amd.ops.pool import convert_avgpools
         count += convert_avgpools(model)
+    if linear == "native":
+        from ddlbench_amd.ops.modules import convert_linears
+        count += convert_linears(model, dtype)
     return count

@@ -1457,6 +1457,120 @@ py::dict line_plan_py(int64_t N, int64_t C, int64_t K, int64_t H, int64_t W,
   return d;
 }
 
+// ---- bf16 Linear (csrc/linear.hip) --------------------------------------
+// A 2-D contiguous, 16-byte aligned bf16 matrix on the device whose inner
+// extent is a multiple of 8; the message names the argument.
+static void check_linear_operand(const torch::Tensor& t, const char* name,
+                                 const char* inner) {
+  TORCH_CHECK(t.is_cuda(), "linear: ", name, " must be on the HIP device");
+  TORCH_CHECK(is_bf16(t), "linear: ", name, " must be bf16");
+  TORCH_CHECK(t.dim() == 2, "linear: ", name, " must be 2-D");
+  TORCH_CHECK(t.is_contiguous(), "linear: ", name, " must be contiguous");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+              "linear: ", name, " must be 16-byte aligned");
+  TORCH_CHECK(t.size(0) >= 1, "linear: ", name, " is empty");
+  TORCH_CHECK(t.size(1) >= 8 && t.size(1) % 8 == 0, "linear: ", name,
+              " needs ", inner, " % 8 == 0, got ", t.size(1));
+}
+
+// x (M,K), w (N,K), bias [N] bf16 or fp32 -> y (M,N) = x w^T + bias, the
+// bias added in fp32 and the sum rounded once.
+torch::Tensor linear_fwd(torch::Tensor x, torch::Tensor w,
+                         c10::optional<torch::Tensor> bias) {
+  check_linear_operand(x, "x", "K");
+  check_linear_operand(w, "w", "K");
+  TORCH_CHECK(w.device() == x.device(), "linear: w must be on x's device");
+  const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
+  TORCH_CHECK(w.size(1) == K, "linear: w has K = ", w.size(1), ", x has ", K);
+  TORCH_CHECK(N % 8 == 0, "linear: w needs N % 8 == 0, got ", N);
+  const void* bptr = nullptr;
+  int bias_f32 = 0;
+  if (bias.has_value() && bias->defined()) {
+    const torch::Tensor& b = *bias;
+    TORCH_CHECK(b.is_cuda() && b.device() == x.device(),
+                "linear: bias must be on x's device");
+    TORCH_CHECK(is_bf16(b) || b.scalar_type() == at::kFloat,
+                "linear: bias must be bf16 or fp32");
+    TORCH_CHECK(b.dim() == 1 && b.size(0) == N && b.is_contiguous(),
+                "linear: bias must be a contiguous [N] vector");
+    bptr = b.data_ptr();
+    bias_f32 = !is_bf16(b);
+  }
+  const LinearPlan pl = linear_plan(M, N, K);
+  auto y = torch::empty({M, N}, x.options());
+  launch_linear_fwd(pl, x.data_ptr(), w.data_ptr(), bptr, bias_f32,
+                    y.data_ptr(), zero_page(x).data_ptr(), M, N, K,
+                    cur_stream());
+  return y;
+}
+
+// dy (M,N), w (N,K) read in place -> dx (M,K) = dy w
+torch::Tensor linear_dgrad(torch::Tensor dy, torch::Tensor w) {
+  check_linear_operand(dy, "dy", "N");
+  check_linear_operand(w, "w", "K");
+  TORCH_CHECK(w.device() == dy.device(), "linear: w must be on dy's device");
+  const int64_t M = dy.size(0), N = dy.size(1), K = w.size(1);
+  TORCH_CHECK(w.size(0) == N, "linear: w has N = ", w.size(0), ", dy has ",
+              N);
+  const LinearPlan pl = linear_plan(M, N, K);
+  auto dx = torch::empty({M, K}, dy.options());
+  launch_linear_dgrad(pl, dy.data_ptr(), w.data_ptr(), dx.data_ptr(),
+                      zero_page(dy).data_ptr(), M, N, K, cur_stream());
+  return dx;
+}
+
+// dy (M,N), x (M,K) -> (dW (N,K) bf16, db [N] in bias_dtype or None). db is
+// summed from the dy tiles the weight-grad stages anyway.
+std::tuple<torch::Tensor, c10::optional<torch::Tensor>> linear_wgrad(
+    torch::Tensor dy, torch::Tensor x, bool want_bias,
+    at::ScalarType bias_dtype) {
+  check_linear_operand(dy, "dy", "N");
+  check_linear_operand(x, "x", "K");
+  TORCH_CHECK(x.device() == dy.device(), "linear: x must be on dy's device");
+  const int64_t M = dy.size(0), N = dy.size(1), K = x.size(1);
+  TORCH_CHECK(x.size(0) == M, "linear: x has M = ", x.size(0), ", dy has ",
+              M);
+  TORCH_CHECK(!want_bias || bias_dtype == at::kBFloat16 ||
+                  bias_dtype == at::kFloat,
+              "linear: bias_dtype must be bf16 or fp32");
+  const LinearPlan pl = linear_plan(M, N, K);
+  auto dw = torch::empty({N, K}, dy.options());
+  c10::optional<torch::Tensor> db;
+  if (want_bias) db = torch::empty({N}, dy.options().dtype(bias_dtype));
+  // per-slab partials, grown to need (at most kLinearWgradPartCap floats);
+  // every element the combine reads is written by the same call
+  static WsCache lws;
+  float* part = nullptr;
+  if (pl.part_floats > 0)
+    part = cached_ws(lws, dy, at::kFloat, pl.part_floats).data_ptr<float>();
+  launch_linear_wgrad(pl, dy.data_ptr(), x.data_ptr(), dw.data_ptr(),
+                      want_bias ? db->data_ptr() : nullptr,
+                      bias_dtype == at::kFloat, part,
+                      zero_page(dy).data_ptr(), M, N, K, cur_stream());
+  return {dw, db};
+}
+
+py::dict linear_plan_py(int64_t M, int64_t N, int64_t K) {
+  TORCH_CHECK(M >= 1 && N >= 8 && K >= 8 && N % 8 == 0 && K % 8 == 0,
+              "linear_plan needs M >= 1, N % 8 == 0 and K % 8 == 0");
+  const LinearPlan pl = linear_plan(M, N, K);
+  auto dir = [](const LinearDirPlan& p) {
+    py::dict d;
+    d["tile"] = p.tile;
+    d["grid"] = py::make_tuple(p.ni, p.nj);
+    d["steps"] = p.steps;
+    d["split"] = p.split;
+    d["rows_per_slab"] = p.r_per;
+    return d;
+  };
+  py::dict d;
+  d["fwd"] = dir(pl.fwd);
+  d["dgrad"] = dir(pl.dgrad);
+  d["wgrad"] = dir(pl.wgrad);
+  d["part_floats"] = pl.part_floats;
+  return d;
+}
+
 // ---- NHWC max-pool ----------------------------------------------------
 std::vector<torch::Tensor> maxpool_fwd(torch::Tensor x, int64_t k,
                                        int64_t stride, int64_t pad) {
@@ -1776,6 +1890,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "NHWC bf16 (1,T)/(T,1) conv weight-grad (bf16 channels_last out)");
   m.def("line_plan", &line_plan_py,
         "host decisions of the line conv launchers for a shape");
+  m.def("linear_fwd", &linear_fwd, "bf16 Linear forward y = x w^T + bias",
+        py::arg("x"), py::arg("w"), py::arg("bias") = py::none());
+  m.def("linear_dgrad", &linear_dgrad, "bf16 Linear data-grad dx = dy w");
+  m.def("linear_wgrad", &linear_wgrad,
+        "bf16 Linear weight-grad (dW, db) from one pass over dy",
+        py::arg("dy"), py::arg("x"), py::arg("want_bias"),
+        py::arg("bias_dtype"));
+  m.def("linear_plan", &linear_plan_py,
+        "host decisions of the Linear launchers for (M, N, K)");
   m.def("ce_fwd", &ce_fwd, "cross-entropy forward");
   m.def("ce_bwd", &ce_bwd, "cross-entropy backward");
   m.def("ls_ce_fwd", &ls_ce_fwd,

@@ -322,6 +322,41 @@ void launch_conv_line_wgrad(const LinePlan&, const void* x, const void* dy,
                             void* dw, float* part, int N, int C, int K, int H,
                             int W, int orient_h, int T, hipStream_t stream);
 
+// ---- linear.hip: y = x W^T + b in bf16, x (M,K), W (N,K), y / dy (M,N)
+// row-major, N % 8 == 0, K % 8 == 0, every operand below 2^31 elements and
+// 16-byte aligned (linear_plan throws otherwise) ---------------------------
+// floats of slab workspace the weight-grad split may use (32 MB)
+constexpr long kLinearWgradPartCap = 8L << 20;
+// One direction's GEMM: ni x nj output tiles of tile x tile, `steps`
+// 64-deep reduction steps per block; the weight-grad cuts its reduction
+// (m) into `split` slabs of r_per rows, one block per tile and slab.
+struct LinearDirPlan {
+  int tile;  // 128 or 64
+  long ni, nj, steps, split, r_per;
+};
+// Every decision of one layer, taken once by linear_plan (pure host code,
+// no device call) and walked by the launchers below.
+struct LinearPlan {
+  LinearDirPlan fwd, dgrad, wgrad;
+  long part_floats;  // wgrad workspace: split * (N*K + N), 0 when split == 1
+};
+LinearPlan linear_plan(long M, long N, long K);
+// bias: [N] bf16 or fp32 (bias_f32), nullptr = none; zero: a 16-byte page
+// of zeros every out-of-range chunk is read from
+void launch_linear_fwd(const LinearPlan&, const void* x, const void* w,
+                       const void* bias, int bias_f32, void* y,
+                       const void* zero, long M, long N, long K,
+                       hipStream_t stream);
+void launch_linear_dgrad(const LinearPlan&, const void* dy, const void* w,
+                         void* dx, const void* zero, long M, long N, long K,
+                         hipStream_t stream);
+// dw: (N,K) bf16, rounded once from the fp32 sum. db: [N] in bf16 or fp32
+// (db_f32), nullptr = not wanted. part: plan.part_floats floats.
+void launch_linear_wgrad(const LinearPlan&, const void* dy, const void* x,
+                         void* dw, void* db, int db_f32, float* part,
+                         const void* zero, long M, long N, long K,
+                         hipStream_t stream);
+
 // ---- maxpool.hip ------------------------------------------------------
 void launch_maxpool_fwd(const void*, void*, unsigned char*, int64_t,
                         int64_t, int, int, int, int, int, int, int,

@@ -568,6 +568,103 @@ def lstm(x: torch.Tensor, w_ih: torch.Tensor, w_hh: torch.Tensor,
     return _lstm_torch(x, w_ih, w_hh, b_ih, b_hh, h0, c0)
 
 
+# ---------------------------------------------------------------- Linear
+class _NativeLinear(torch.autograd.Function):
+    """y = x W^T + b on the kernels of csrc/linear.hip over 2-D, contiguous,
+    16-byte aligned operands. Backward launches the data-grad only when x
+    needs a gradient and the weight-grad (which also yields db, from the same
+    pass over dy) only when the weight or the bias does."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        y = _ops.require_extension().linear_fwd(x, weight, bias)
+        need = ctx.needs_input_grad
+        need_b = bias is not None and need[2]
+        ctx.save_for_backward(x if need[1] or need_b else None,
+                              weight if need[0] else None)
+        ctx.bias_dtype = bias.dtype if need_b else None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        ext = _ops.require_extension()
+        x, weight = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dy = _aligned16(dy)
+        dx = ext.linear_dgrad(dy, weight) if need[0] else None
+        dw = db = None
+        if x is not None:
+            want_b = ctx.bias_dtype is not None
+            dw, db = ext.linear_wgrad(dy, x, want_b,
+                                      ctx.bias_dtype or torch.bfloat16)
+            if not need[1]:
+                dw = None
+        return dx, dw, db
+
+
+def _linear_native_reject(x, weight, bias) -> Optional[str]:
+    """Why the native kernels cannot run these tensors, or None."""
+    if x.device.type != "cuda":
+        return f"a {x.device.type} tensor (the kernels are HIP only)"
+    if x.dtype != torch.bfloat16 or weight.dtype != torch.bfloat16:
+        return (f"{x.dtype} input with {weight.dtype} weights (bf16 only; "
+                "there is no fp32 MFMA path)")
+    if bias is not None and bias.dtype not in (torch.bfloat16, torch.float32):
+        return f"a {bias.dtype} bias (bf16 or fp32)"
+    if weight.dim() != 2 or x.dim() < 1 or x.size(-1) != weight.size(1):
+        return (f"x {tuple(x.shape)} with weight {tuple(weight.shape)} "
+                "(x's last dimension must be the weight's in_features)")
+    N, K = weight.shape
+    if K % 8 != 0 or N % 8 != 0:
+        return (f"in_features = {K}, out_features = {N} (both must be "
+                "multiples of 8: the kernels move 16-byte chunks)")
+    if x.numel() == 0:
+        return "an empty input"
+    if max(x.numel(), weight.numel(), x.numel() // K * N) >= 2 ** 31:
+        return "an operand of 2^31 elements or more (32-bit kernel offsets)"
+    return None
+
+
+def linear(x: torch.Tensor, weight: torch.Tensor,
+           bias: Optional[torch.Tensor] = None,
+           backend: str = "auto") -> torch.Tensor:
+    """``F.linear``: y = x W^T + b for x (..., K) of any leading shape and
+    strides, weight (N, K) and bias (N,).
+
+    The native path (bf16 on a GPU, K and N multiples of 8, bias bf16 or
+    fp32) runs the MFMA kernels of csrc/linear.hip, forward and backward:
+    the bias is added in the fp32 accumulator and every output is rounded
+    once. x is flattened to 2-D and copied only when it is not contiguous
+    or not 16-byte aligned. Anything else takes ``F.linear`` under "auto"
+    and raises NotImplementedError under "native"."""
+    native = _ops.use_native(x, backend)
+    if native:
+        why = _linear_native_reject(x, weight, bias)
+        if why is not None:
+            if backend == "native":
+                raise NotImplementedError(
+                    f"native linear does not support {why}; pass "
+                    "backend=\"torch\" for the library GEMM")
+            native = False
+    if not native:
+        return F.linear(x, weight, bias)
+    N, K = weight.shape
+    x2 = _aligned16(x.reshape(-1, K))
+    weight = _aligned16(weight)
+    if bias is not None:
+        bias = bias.contiguous()
+    tensors = (x2, weight, bias)
+    if torch.is_grad_enabled() and any(
+            t is not None and t.requires_grad for t in tensors):
+        y = _NativeLinear.apply(*tensors)
+    else:
+        # nothing to differentiate (decode): save nothing
+        y = _ops.require_extension().linear_fwd(
+            x2.detach(), weight.detach(),
+            bias.detach() if bias is not None else None)
+    return y.view(*x.shape[:-1], N)
+
+
 # ------------------------------------------------------- depthwise conv3x3
 class _FusedDWConv3x3(torch.autograd.Function):
     @staticmethod

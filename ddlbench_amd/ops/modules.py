@@ -5,7 +5,8 @@ model zoo with one fused op; ``DepthwiseConv3x3`` replaces
 Conv2d(groups=channels). Both keep plain-PyTorch semantics (state dict
 compatible with nn.BatchNorm2d / nn.Conv2d field names). ``LSTM`` is
 nn.LSTM with a choice of recurrence backend, the "lstm" row of
-``ops.switches`` (DDLB_LSTM)."""
+``ops.switches`` (DDLB_LSTM); ``Linear`` is nn.Linear with a choice of GEMM,
+by argument only."""
 
 from __future__ import annotations
 
@@ -15,7 +16,7 @@ import torch
 import torch.nn as nn
 
 from ddlbench_amd.ops import check_backend, functional as NF
-from ddlbench_amd.ops.switches import resolve
+from ddlbench_amd.ops.switches import check, resolve
 
 # module-level default backend — engines set this once from the config
 _DEFAULT_BACKEND = "auto"
@@ -160,6 +161,57 @@ class LSTM(nn.LSTM):
         return NF.lstm(input, self.weight_ih_l0, self.weight_hh_l0,
                        self.bias_ih_l0, self.bias_hh_l0, hx,
                        backend="native")
+
+
+class Linear(nn.Linear):
+    """``torch.nn.Linear`` with a choice of GEMM: same parameters, same
+    registration order (so the same seeded initial values) and the same
+    ``state_dict`` keys. ``backend`` is "library" (default, ``F.linear``) or
+    "native": ``NF.linear``'s MFMA kernels, forward and backward, which raise
+    NotImplementedError for anything they cannot run. There is no
+    environment switch."""
+
+    def __init__(self, *args, backend: str = "library", **kwargs):
+        super().__init__(*args, **kwargs)
+        self.backend = check("linear", backend, ("library", "native"))
+
+    def forward(self, input):
+        if self.backend == "library":
+            return super().forward(input)
+        return NF.linear(input, self.weight, self.bias, backend="native")
+
+    def extra_repr(self) -> str:
+        return f"{super().extra_repr()}, backend={self.backend}"
+
+
+def linear_eligible(m: nn.Module, dtype=torch.bfloat16) -> bool:
+    """True for an nn.Linear the kernels of csrc/linear.hip can run: bf16,
+    in_features and out_features multiples of 8."""
+    return (type(m) in (nn.Linear, Linear)
+            and dtype == torch.bfloat16
+            and m.in_features % 8 == 0
+            and m.out_features % 8 == 0)
+
+
+def convert_linears(model: nn.Module, dtype=torch.bfloat16) -> int:
+    """Swap every linear_eligible nn.Linear child for a native ``Linear``
+    that shares its Parameter objects (an optimizer built before the call
+    keeps working). Returns the number of conversions."""
+    count = 0
+    for parent in model.modules():
+        for name, child in list(parent.named_children()):
+            if type(child) is not nn.Linear or not linear_eligible(child,
+                                                                   dtype):
+                continue
+            new = Linear(child.in_features, child.out_features,
+                         bias=child.bias is not None, backend="native",
+                         device="meta")
+            new.weight = child.weight
+            new.bias = child.bias
+            new.train(child.training)
+            setattr(parent, name, new)
+            count += 1
+    return count
 
 
 class CrossEntropyLoss(nn.Module):
